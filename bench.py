@@ -10,13 +10,19 @@ Jacobian assembly of a one-experiment Project on top (64 rows x 40 parameters pe
 value = accepted integrator steps of all trajectories of all ranks / wall time.
 
     python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2 --dump-outputs DIR    + the last timed step's outputs as DIR/*.npy
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full                + everything below
     python bench.py --gpus N ...          spawns N ranks itself (torch.distributed.run, one process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value, ms_per_step, ...;
+`roofline` and `cpu_baseline` are null).  Everything else is measured only with --full.
 
 Multi-GPU: the ensemble is sharded by vector index (weak scaling: 4096 vectors per GPU, no
 data-path collective); RCCL carries only the all-gather of the per-vector residual norms.
 
-At N = 1 the line also carries, under "configs", BASELINE.json's other configurations -- configs[1]
+With --full the line carries the rooflines and the CPU baselines with the parity of the timed pass, and
+at N = 1 also, under "configs", BASELINE.json's other configurations -- configs[1]
 (state only), configs[3] (8-experiment Project), configs[4] (stiff 50-state model) -- each with its own
 `roofline` and `cpu_baseline` objects, "fit" (end-to-end multi-start fitting against the reference's
 serial leastsq pattern) and "dense" (the MFMA question).  `--only NAME` runs one of them alone (what the
@@ -510,6 +516,31 @@ def write_full(full, path=None):
         return None
 
 
+DUMP_SEED = 0
+DUMP_J_VECTORS = 1024            # Jacobian rows of this many vectors: 1024 x 64 x 40 f64 = 21 MB
+DUMP_MAX_VECTORS = 16384         # every other array (1080 B per vector here): at most 17.7 MB
+
+
+def dump_outputs(dirname, host, suffix=''):
+    """What one pass hands its caller -- simulated rows, residual rows, Jacobian, scale factors, norms, status and
+    accepted steps per vector -- as DIR/<name><suffix>.npy in float64, at most 64 MB in all.  Arrays over more vectors
+    than the caps above are cut to a fixed seeded sample of vectors, whose indices are written next to them
+    (J_vectors, vectors)."""
+    os.makedirs(dirname, exist_ok=True)
+    V = len(host['norms'])
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = (lambda n: np.arange(V) if V <= n else np.sort(rng.choice(V, size=n, replace=False)))
+    rows, jrows = pick(DUMP_MAX_VECTORS), pick(DUMP_J_VECTORS)
+    arrays = {name: host[name][rows] for name in ('sims', 'res', 'sf', 'norms', 'status', 'nsteps')}
+    arrays['J'] = host['J'][jrows]
+    arrays['J_vectors'] = jrows
+    if len(rows) < V:
+        arrays['vectors'] = rows
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + suffix + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -527,7 +558,14 @@ def main():
     ap.add_argument('--full-out', default=None, help="where the full record goes (default gpurun_out/bench_full.json); "
                     "stdout carries ONE compact line")
     ap.add_argument('--cpu-baseline-only', action='store_true', help="time the CPU oracle and exit (no GPU needed)")
+    ap.add_argument('--full', action='store_true', help="everything beyond the headline figure: CPU baselines, parity of "
+                    "the timed pass against the oracle, the product-default and host-inclusive passes, the rooflines, "
+                    "the side configurations and kernel variants, and the full record (--full-out)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help="after the timed steps, write what the last "
+                    "step computed as DIR/<name>.npy (float64; a fixed seeded sample of the Jacobian rows)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     global T_START
     T_START = time.perf_counter()
 
@@ -546,7 +584,8 @@ def main():
         raise SystemExit("bench.py --gpus %d started inside a world of %d ranks: launch with "
                          "torch.distributed.run --nproc-per-node %d (or plain `python bench.py --gpus %d`, which "
                          "spawns the ranks itself)" % (args.gpus, world, args.gpus, args.gpus))
-    with_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and args.only is None
+    with_cpu = ((args.full or args.cpu_baseline_only) and rank == 0 and world == 1 and not args.no_cpu_baseline
+                and args.only is None)
     cpu_all = None
     if with_cpu:
         from sysbio_modeling_amd import models_zoo as _mz
@@ -661,6 +700,10 @@ def main():
         total_steps_per_pass = float(steps_per_pass)
         per_rank_ms, world_seen, backend, norms_ok, nccl_version = [1e3 * dt / args.steps], 1, None, True, None
     value = total_steps_per_pass * args.steps / dt
+    if args.dump_outputs:
+        # the buffers still hold the last timed step; every rank writes its own block
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in out.items()},
+                     suffix='_rank%d' % rank if world > 1 else '')
     if args.only == 'headline':
         emit({"headline": {"ms_per_step": 1e3 * dt / args.steps, "value": value,
                            "steps_per_pass": total_steps_per_pass}, "build": dict(_CURRENT_STAMPS)})
@@ -669,7 +712,7 @@ def main():
     # ---- what a user's call runs: explicit_method='auto' picks the pair by tolerance and batch (DOP853 at these defaults); the same
     # pass (gather + integrate + assemble) timed with it -- its steps are not comparable with DOPRI45's, its ms per pass is ----
     product_default = None
-    if world == 1 and args.method == 'dopri45':
+    if args.full and world == 1 and args.method == 'dopri45':
         try:
             pick = _lib.predict_explicit_pair(tol['rtol'], int(V), 1, 2)[0]
             o2 = _lib.make_opts(pick, rtol=(0.1 if pick == 'dop853' else 1.0) * tol['rtol'], atol=tol['atol'])
@@ -696,7 +739,7 @@ def main():
 
     # ---- SURVEY.md section 8(d)'s host-inclusive figure: P upload and download of the sampled rows / norms ----
     host_incl = None
-    if world == 1:
+    if args.full and world == 1:
         th_pin = torch.from_numpy(theta).pin_memory()
         res_pin = torch.empty((V, R), dtype=f64).pin_memory()
         nrm_pin = torch.empty((V,), dtype=f64).pin_memory()
@@ -723,31 +766,33 @@ def main():
                              "the Jacobian (V x 64 x 40 f64 = 84 MB per pass); never reported as `value`")
 
     # ---- roofline of the dominant kernel: the sensitivity integrator alone, HIP events on its stream ----
-    dm = model.device_model
-    theta_p = torch.exp(th)  # all parameters Global and in model order: p = exp(theta)
-    tg = torch.from_numpy(np.concatenate([[0.0], t_meas])).to(dev)
-    Yk = torch.empty((V, len(tg), 20), dtype=f64, device=dev)
-    Sk = torch.empty((V, len(tg), 20, 40), dtype=f64, device=dev)
-    ns_k = torch.empty((V,), dtype=i32, device=dev)
-    for _ in range(max(1, args.warmup)):
-        dm.sens_dev(theta_p, tg, None, opts, Yk, Sk, None, ns_k, None)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize(dev)
-    e0.record()
-    for _ in range(args.steps):
-        dm.sens_dev(theta_p, tg, None, opts, Yk, Sk, None, ns_k, None)
-    e1.record()
-    torch.cuda.synchronize(dev)
-    k_ms = e0.elapsed_time(e1) / args.steps
-    k_steps = int(ns_k.sum().item())
-    kkey = 'sens_rowgroup_cascade20_%s' % args.method
-    roofline = hbm_roofline("sbm_sens_rowgroup_kernel<cascade20,%s>" % args.method, kkey, k_ms, k_steps,
-                            BYTES_PER_STEP,
-                            "algorithmic bytes (2*8*820 B per accepted step) / kernel time; the kernel keeps the "
-                            "state in VGPRs, so real HBM traffic ('traffic', PMC) is far below this figure and the "
-                            "binding resource is VALU issue: see roofline_valu_issue")
-    roofline_valu = valu_roofline(kkey, k_ms, k_steps)
-    roofline["achieved_fp64"] = fp64_rate(*flops_per_step(gm, args.method), k_steps / (k_ms * 1e-3))
+    roofline = roofline_valu = None
+    if args.full:
+        dm = model.device_model
+        theta_p = torch.exp(th)  # all parameters Global and in model order: p = exp(theta)
+        tg = torch.from_numpy(np.concatenate([[0.0], t_meas])).to(dev)
+        Yk = torch.empty((V, len(tg), 20), dtype=f64, device=dev)
+        Sk = torch.empty((V, len(tg), 20, 40), dtype=f64, device=dev)
+        ns_k = torch.empty((V,), dtype=i32, device=dev)
+        for _ in range(max(1, args.warmup)):
+            dm.sens_dev(theta_p, tg, None, opts, Yk, Sk, None, ns_k, None)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(dev)
+        e0.record()
+        for _ in range(args.steps):
+            dm.sens_dev(theta_p, tg, None, opts, Yk, Sk, None, ns_k, None)
+        e1.record()
+        torch.cuda.synchronize(dev)
+        k_ms = e0.elapsed_time(e1) / args.steps
+        k_steps = int(ns_k.sum().item())
+        kkey = 'sens_rowgroup_cascade20_%s' % args.method
+        roofline = hbm_roofline("sbm_sens_rowgroup_kernel<cascade20,%s>" % args.method, kkey, k_ms, k_steps,
+                                BYTES_PER_STEP,
+                                "algorithmic bytes (2*8*820 B per accepted step) / kernel time; the kernel keeps the "
+                                "state in VGPRs, so real HBM traffic ('traffic', PMC) is far below this figure and the "
+                                "binding resource is VALU issue: see roofline_valu_issue")
+        roofline_valu = valu_roofline(kkey, k_ms, k_steps)
+        roofline["achieved_fp64"] = fp64_rate(*flops_per_step(gm, args.method), k_steps / (k_ms * 1e-3))
 
     result = {
         "metric": "ensemble ODE-steps/sec (20-state model + fwd sens)",
@@ -782,14 +827,14 @@ def main():
     elif rank == 0:
         result["cpu_baseline"] = None
 
-    if world > 1 and not args.no_extras:
+    if args.full and world > 1 and not args.no_extras:
         # the configuration BASELINE names for the multi-GPU run, sharded the same way (collective: all ranks)
         try:
             c3s = bc.run_configs3_sharded(model, gm, dev, world, rank, steps=max(2, args.steps // 2), warmup=1)
         except Exception as e:   # noqa: BLE001
             c3s = {"error": repr(e)[:300]}
         result["configs"] = {"configs3_sharded": c3s}
-    if not args.no_extras and rank == 0 and world == 1:
+    if args.full and not args.no_extras and rank == 0 and world == 1:
         # BASELINE.json's other configurations, each with its own roofline and CPU leg; then kernel variants
         cfgs = {}
         for name in bc.ORDER:
@@ -811,7 +856,7 @@ def main():
     if rank == 0:
         result["build"] = dict(_CURRENT_STAMPS)
         result["wall_seconds"] = time.perf_counter() - T_START
-        path = write_full(result, args.full_out)
+        path = write_full(result, args.full_out) if (args.full or args.full_out) else None
         emit(compact_line(result, path))
     if world > 1:
         dist.barrier()   # rank 0 arrives late

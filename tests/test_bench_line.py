@@ -1,7 +1,8 @@
 """The driver keeps only a tail of bench.py's stdout: the LAST line must be a compact JSON object (round 3's line had
 grown to 24 KB and was cut mid-object -- BENCH_r03.parsed = null).  bench.compact_line builds that line from the full
 record; these tests feed it canned full records (round 3's own 24 KB record, and synthetic worst cases) and check the
-size cap, the round trip and the keys the contract names."""
+size cap, the round trip and the keys the contract names.  The last two check --dump-outputs and a plain run (what
+--full adds stays out of it)."""
 import copy
 import json
 import os
@@ -121,3 +122,50 @@ def test_round4_record_and_its_committed_line_agree():
     assert back['roofline']['traffic'] is not None and back['cpu_baseline']['parity_of_timed_pass']['gpu_within_1e-8_of_tight'] is True
     assert back['configs']['configs4']['roofline']['bound'] == 'instruction_issue'
     assert back['product_default']['integrator'] in ('dop853', 'dopri45')
+
+
+def test_dump_outputs_float64_bounded_and_seeded(tmp_path):
+    """--dump-outputs: every array of the pass as float64 .npy; the Jacobian cut to a fixed seeded sample of vectors whose
+    indices are written with it, the same sample on every run; the whole dump under 64 MB."""
+    import numpy as np
+    V, R, q = 4096, 64, 40
+    rng = np.random.default_rng(3)
+    host = dict(sims=rng.random((V, R)), res=rng.random((V, R)), J=rng.random((V, R, q)), sf=rng.random((V, 4)),
+                norms=rng.random(V), status=np.zeros(V, np.int32), nsteps=rng.integers(900, 1000, V).astype(np.int32))
+    names = bench.dump_outputs(str(tmp_path / 'a'), host)
+    bench.dump_outputs(str(tmp_path / 'b'), host)
+    assert set(names) >= {'sims', 'res', 'J', 'sf', 'norms', 'status', 'nsteps', 'J_vectors'}
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / 'a' / (n + '.npy')), np.load(tmp_path / 'b' / (n + '.npy'))
+        assert a.dtype == np.float64 and np.array_equal(a, b), n
+        total += (tmp_path / 'a' / (n + '.npy')).stat().st_size
+    assert total <= 64 << 20
+    rows = np.load(tmp_path / 'a' / 'J_vectors.npy').astype(int)
+    assert len(rows) == bench.DUMP_J_VECTORS and len(set(rows)) == len(rows)
+    assert np.array_equal(np.load(tmp_path / 'a' / 'J.npy'), host['J'][rows])
+    assert np.array_equal(np.load(tmp_path / 'a' / 'nsteps.npy'), host['nsteps'])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: ONE line with the contract's keys, `steps`
+    = K, nothing of --full measured; the last timed step's outputs in DIR, every vector integrated."""
+    import subprocess
+    import sys
+    import numpy as np
+    p = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--dump-outputs', str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                       timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in d, k
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0 and d['value'] > 0 and d['dtype'] == 'f64'
+    assert d['roofline'] is None and d['cpu_baseline'] is None and d['full'] is None and 'configs' not in d
+    res, nsteps = np.load(tmp_path / 'res.npy'), np.load(tmp_path / 'nsteps.npy')
+    assert res.shape == (4096, 64) and np.all(np.isfinite(res)) and np.all(np.load(tmp_path / 'status.npy') == 0)
+    assert nsteps.sum() == pytest.approx(d['config']['accepted_steps_per_pass'], rel=1e-5)    # (the line has 6 digits)
+    assert np.load(tmp_path / 'J.npy').shape == (bench.DUMP_J_VECTORS, 64, 40)

@@ -130,8 +130,8 @@ def test_two_rccl_ranks_one_per_device(tmp_path):
 
 
 def test_bench_multi_rank_line_on_one_gpu():
-    """`python bench.py --gpus 2` end to end in rehearsal mode (SBM_BENCH_REHEARSAL=1: both ranks on GPU 0, gloo instead of
-    RCCL -- RCCL refuses two ranks on one device): the launcher spawns its ranks itself, rank 0 prints ONE JSON line with
+    """`python bench.py --gpus 2 --full` end to end in rehearsal mode (SBM_BENCH_REHEARSAL=1: both ranks on GPU 0, gloo
+    instead of RCCL -- RCCL refuses two ranks on one device): the launcher spawns its ranks itself, rank 0 prints ONE JSON line with
     the weak-scaling headline AND the configuration BASELINE.json names for the multi-GPU run, configs[3], sharded by
     vector over the ranks (strong scaling), every rank finding its own block in the gathered norms."""
     import json
@@ -141,7 +141,8 @@ def test_bench_multi_rank_line_on_one_gpu():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SBM_BENCH_REHEARSAL='1')
     p = subprocess.run([sys.executable, os.path.join(repo, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                        '--no-cpu-baseline'], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
+                        '--full', '--no-cpu-baseline'], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env,
+                       timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1

@@ -3,7 +3,6 @@
 OdeModel(jittable_model.model, sens_jittable_model.sens_model, n_vars, ordered_params)
 (tests/test_OdeModel.py:12-18), works without going through this package's generator."""
 import importlib.util
-import os
 
 import numpy as np
 import pytest
@@ -11,8 +10,6 @@ import sympy
 
 from sysbio_modeling_amd.symbolic import ingest, zoo_model, GeneratedModel
 from tests.support import plain_models as pm
-
-REF_UTILS = '/root/reference/tests/test_utils'
 
 
 def test_spec_from_hand_written_callable():
@@ -135,18 +132,41 @@ def test_static_loops_and_branches_unroll_to_the_straight_line_form():
     assert sympy.simplify(c.equations['y1'] - (sympy.Symbol('c') * ys[0] + sympy.Symbol('d') * ys[1])) == 0
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_UTILS), reason="the reference tree exists in the build container only")
-def test_the_references_own_emitted_fixtures_are_read():
-    """tests/test_utils/jittable_model.py / sens_jittable_model.py / jittable_mm_model.py / sens_jittable_mm_model.py
-    of the reference: same equations as the zoo restatements of the two known-answer systems."""
-    def load(name):
-        s = importlib.util.spec_from_file_location('ref_' + name, os.path.join(REF_UTILS, name + '.py'))
+def _emitted_form_modules(z):
+    """Module texts of ``model`` and ``sens_model`` for the spec ``z`` in the form the reference's generator emits
+    (symbolic/sympy_tools.py:100-111,185-195 of the reference: ``name = p[i]``, ``name = y[i]``, then
+    ``yout[i] = (expression)``; sensitivity variables ``sens_<var>_<param> = y[n + i*k + j]``), written by sympy."""
+    ys = [sympy.Symbol(v) for v in z.variables]
+    ps = [sympy.Symbol(q) for q in z.params]
+    n, k = len(ys), len(ps)
+    sens = [[sympy.Symbol('sens_%s_%s' % (v.name.lstrip('_'), q.name)) for q in ps] for v in ys]
+    f = [sympy.sympify(z.equations[v]) for v in z.variables]
+    head = ["    %s = p[%d]" % (q, j) for j, q in enumerate(ps)] + [""] + ["    %s = y[%d]" % (v, i) for i, v in enumerate(ys)] + [""]
+    rows = ["    yout[%d] = (%s)" % (i, fi) for i, fi in enumerate(f)]
+    plain = "ordered_params = %r\nn_vars = %d\n\n\ndef model(y, t, yout, p):\n%s\n" % (z.params, n, "\n".join(head + rows))
+    sv = ["    %s = y[%d]" % (sens[i][j], n + i * k + j) for i in range(n) for j in range(k)] + [""]
+    srows = ["    yout[%d] = (%s)" % (n + i * k + j, sympy.expand(sum(sympy.diff(f[i], ys[m]) * sens[m][j] for m in range(n))
+                                                                    + sympy.diff(f[i], ps[j])))
+             for i in range(n) for j in range(k)]
+    sensmod = "\n\ndef sens_model(y, t, yout, p):\n%s\n" % "\n".join(head + sv + rows + [""] + srows)
+    return plain, sensmod
+
+
+def test_the_references_own_emitted_fixtures_are_read(tmp_path):
+    """The reference's emitted form of its two known-answer systems (its tests/test_utils/jittable_model.py,
+    sens_jittable_model.py, jittable_mm_model.py, sens_jittable_mm_model.py), written from the zoo restatements into
+    module files: read back from their source, they give the zoo's equations and parameter order."""
+    def load(name, text):
+        path = tmp_path / (name + '.py')
+        path.write_text(text)
+        s = importlib.util.spec_from_file_location('emitted_' + name, str(path))
         m = importlib.util.module_from_spec(s)
         s.loader.exec_module(m)
         return m
     for plain, sens, n, params, zoo in (('jittable_model', 'sens_jittable_model', 1, ['k_deg', 'k_synt'], 'simple'),
                                         ('jittable_mm_model', 'sens_jittable_mm_model', 2, None, 'michaelis_menten')):
-        mod, smod = load(plain), load(sens)
+        text, sens_text = _emitted_form_modules(zoo_model(zoo).spec)
+        mod, smod = load(plain, text), load(sens, sens_text)
         params = params or list(mod.ordered_params)
         spec = ingest.spec_from_callables(mod.model, smod.sens_model, n, params)
         z = zoo_model(zoo).spec
