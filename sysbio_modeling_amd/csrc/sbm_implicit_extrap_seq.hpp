@@ -64,10 +64,20 @@ struct SbmIexSeqPlan {
   static constexpr int NROWP = LPG * RPG;                        // rows incl. padding
   static constexpr int W = 2 + M::RL_MAXJP;                      // per row: 1 / M_ii, h J_y[i][i-1] / M_ii, J_p[slot ...]
   static constexpr int LW = RPG * W + ((RPG * W) & 1);           // doubles per lane and step (16-byte blocks)
-  // rotated columns (ROT): a step's table = RC[64][2] (1 / M_ii, h J_y[i][i-1] / M_ii by row) + A[64] (the row's J_p entry)
+  // rotated columns (ROT): a step's table = RC[64][2] (1 / M_ii, h J_y[i][i-1] / M_ii by row) + A[64] (the row's J_p entry).
+  // A column reads the coefficient rows r0 .. r0 + NV - 1 with no modulo (r0 <= NV - 1).  Row NV must cut the recurrence,
+  // i.e. have a zero sub-diagonal coefficient, and phase A writes it in every launch: a padded row (NV < NROWP; phase A
+  // evaluates row 0 there, which has no sub-diagonal entry) or one of the zero rows NROWP .. 63 that phase A also writes.
+  // At NV = 64 row NV would be A[0], A[1]: no rotation.  (The rows read behind the cut meet a column that is exactly zero
+  // there: they only have to be finite.)
   static constexpr int ROT_STEP_DOUBLES = 128 + 64;
-  static constexpr bool ROT_OK = M::IM_ROT && M::RL_MAXJP == 1 && (RPG % 2) == 0;
+  static constexpr bool ROT_OK = M::IM_ROT && M::RL_MAXJP == 1 && (RPG % 2) == 0 && M::NV < 64;
+  static constexpr int ROT_ZROWS = (64 - NROWP) / LPG;           // zero rows NROWP .. 63 of RC per lane of a group
+  static constexpr int ROT_ROW_MAX = 2 * (M::NV - 1);            // the last coefficient row a column (or an idle lane) reads
   static constexpr int NRING = 5;                                // Euler steps' tables in LDS at once (prefetch ring)
+  // the ring + a guard behind its last entry for the rows a column of that entry reads past the entry's end
+  static constexpr int RING_DOUBLES = (NRING - 1) * ROT_STEP_DOUBLES +
+      (2 * ROT_ROW_MAX + 2 > ROT_STEP_DOUBLES + 16 ? 2 * ROT_ROW_MAX + 2 : ROT_STEP_DOUBLES + 16);
   static constexpr int KMAX = 8;
   static constexpr int NSTEP = KMAX * (KMAX + 1) / 2;
   static constexpr int STEP_DOUBLES = LPG * LW;                  // one Euler step's table
@@ -82,8 +92,9 @@ struct SbmIexSeqShared : SbmIexShared<M> {
   double YG[P::NG][64];                                // the iterate of every group's sequence, by row
   double TG[P::KMAX][64];                              // T_j (state) of every sequence, by row
   // rotated columns: a ring of NRING step tables (RC[64][2] + A[64] each) that LDS-direct loads fill ahead of their use,
-  // + a guard (a lane reads up to row 2 NV - 2 of "its" table: what lies behind a table only has to be finite)
-  __attribute__((aligned(16))) double RING[P::ROT_OK ? P::NRING * P::ROT_STEP_DOUBLES + 16 : 2];
+  // + a guard (a lane reads up to row ROT_ROW_MAX = 2 NV - 2 of "its" table: what lies behind a table only has to be
+  // finite; the guard is zeroed per trajectory and no load writes it)
+  __attribute__((aligned(16))) double RING[P::ROT_OK ? P::RING_DOUBLES : 2];
 };
 
 template <class M>
@@ -148,11 +159,11 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
     const int zl = lane < Sh::ZC ? lane : ZS - 1;
 
     // ROT: register k of this lane's column = row (r0 + k) mod NV, r0 = the row of the column's one J_p entry (rows above
-    // it are structurally zero in a chain); idle lanes sit on the zero rows of the coefficient table
-    const int r0 = ROT ? (has_col ? M::im_r0(has_col ? col : 0) : 64) : 0;
+    // it are structurally zero in a chain); idle lanes run a zero column from row 0 (their J_p term is multiplied by 0)
+    const int r0 = ROT ? (has_col ? M::im_r0(has_col ? col : 0) : 0) : 0;
     const int jq = ROT ? M::im_jpq(has_col ? col : 0) : 0;
     if constexpr (ROT) {
-      for (int i = lane; i < Pl::NRING * Pl::ROT_STEP_DOUBLES + 16; i += 64) sh.RING[i] = 0.0;
+      for (int i = lane; i < Pl::RING_DOUBLES; i += 64) sh.RING[i] = 0.0;
     }
     double yn[1], ydot[1];
 #pragma unroll
@@ -230,6 +241,10 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
               double* const da = dst - (size_t)gl * RPG * 2 + 128 + (size_t)gl * RPG;
 #pragma unroll
               for (int r = 0; r < RPG; r += 2) *reinterpret_cast<double2*>(da + r) = double2{tw[r * W + 2], tw[(r + 1) * W + 2]};
+              // rows NROWP .. 63 of RC: zeros (the cut row of NV = NROWP; rows read behind the cut), never stale scratch
+              double* const dz = dst - (size_t)gl * RPG * 2 + 2 * (Pl::NROWP + gl * Pl::ROT_ZROWS);
+#pragma unroll
+              for (int r = 0; r < Pl::ROT_ZROWS; ++r) *reinterpret_cast<double2*>(dz + 2 * r) = double2{0.0, 0.0};
             } else {
 #pragma unroll
               for (int q = 0; q < LW; q += 2) *reinterpret_cast<double2*>(dst + q) = double2{tw[q], tw[q + 1]};
@@ -439,10 +454,15 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
           // step spent waiting).  Two loads per step: RC by all lanes, A by lanes 0 .. 31.  Nothing else in this loop may
           // touch vector memory (the counts below assume it; tests/test_seq_kernel_isa.py reads the ISA).
           constexpr int NR = Pl::NRING, ENTRY = Pl::ROT_STEP_DOUBLES;
+          // the furthest read of a lane: row r0 + NV - 1 <= ROT_ROW_MAX of the ring's last entry, both doubles of it
+          static_assert((NR - 1) * ENTRY + 2 * Pl::ROT_ROW_MAX + 1 < (int)(sizeof(sh.RING) / sizeof(double)), "ring guard");
+          static_assert(Pl::NROWP + Pl::ROT_ZROWS * Pl::LPG == 64 && NV < 64, "row NV cuts the rotated recurrence");
           const double colmask = has_col ? 1.0 : 0.0;
           const unsigned ring0 = (unsigned)(size_t)(&sh.RING[0]);
+          const int n_euler = K * (K + 1) / 2;
+          // (the loads behind the last step repeat it: every entry of the ring holds a table phase A wrote in this macro step)
           auto issue = [&](int kk) {
-            const int kc = kk < Pl::NSTEP ? kk : Pl::NSTEP - 1;
+            const int kc = kk < n_euler ? kk : n_euler - 1;
             const double* g = tblock + (size_t)kc * ENTRY + 2 * lane;
             const unsigned dst = ring0 + (unsigned)((kk % NR) * ENTRY * 8);
             // (the instruction offset moves the global AND the LDS address: A follows RC at byte 1024 on both sides)
@@ -453,7 +473,6 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
           };
 #pragma unroll 1
           for (int kk = 0; kk < NR - 1; ++kk) issue(kk);
-          const int n_euler = K * (K + 1) / 2;
           int j = 1, m = 0;
           double h = Hs;
           double zs[NV];

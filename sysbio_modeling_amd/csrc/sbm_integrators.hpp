@@ -2022,6 +2022,9 @@ static hipError_t sbm_scratch_for(hipStream_t stream, size_t need, SbmScratch** 
     s.bytes = 0;
     e = hipMalloc(&s.p, need);
     if (e != hipSuccess) { s.p = nullptr; return e; }
+    // zeroed once, on the stream: a first launch sees the same bytes whatever the allocator hands out
+    e = hipMemsetAsync(s.p, 0, need, stream);
+    if (e != hipSuccess) { (void)hipFree(s.p); s.p = nullptr; return e; }
     s.bytes = need;
   }
   *out = &s;

@@ -163,7 +163,7 @@ CASCADE_MEASURED_SPECIES = (4, 9, 14, 19)
 # ----------------------------------------------------------------------------
 # stiff50: 50-state signalling cascade with rate constants spanning 1e6
 # ----------------------------------------------------------------------------
-def stiff_spec(n=50, name=None, fixed_deactivation=True):
+def stiff_spec(n=50, name=None, fixed_deactivation=True, unused=None):
     """Activation cascade with saturating deactivation, every species with its own time scale
     (BASELINE configs[4]):
 
@@ -179,6 +179,8 @@ def stiff_spec(n=50, name=None, fixed_deactivation=True):
     (deactivation strengths, nominal 0.5); with ``fixed_deactivation`` the b_i are 'fixed' parameters
     (no sensitivity columns): k = n sensitivity parameters, N = n + n*n = 2550 coupled ODEs at n = 50, as
     SURVEY.md section 8(d) sizes config 5.
+    ``unused`` ('leading' / 'trailing'): one more sensitivity parameter 'unused', first or last in param_order, that no
+    equation refers to (a sensitivity column without a J_p entry).
     """
     xs = [Symbol('x%d' % i) for i in range(n)]
     a = [Symbol('a%d' % i) for i in range(n)]
@@ -188,9 +190,21 @@ def stiff_spec(n=50, name=None, fixed_deactivation=True):
     eq['x0'] = a[0] * ((1 - xs[0]) - b[0] * xs[0] / (half + xs[0]))
     for i in range(1, n):
         eq['x%d' % i] = a[i] * (xs[i - 1] * (1 - xs[i]) - b[i] * xs[i] / (half + xs[i]))
-    return ModelSpec(name=name or ('stiff%d' % n), variables=[str(x) for x in xs],
-                     params=[str(s) for s in a] + [str(s) for s in b], equations=eq,
+    params = [str(s) for s in a] + [str(s) for s in b]
+    if unused is not None:
+        params = ['unused'] + params if unused == 'leading' else params + ['unused']
+    return ModelSpec(name=name or ('stiff%d' % n), variables=[str(x) for x in xs], params=params, equations=eq,
                      fixed=[str(s) for s in b] if fixed_deactivation else [])
+
+
+def seq_layout_specs():
+    """The stiff chains of the seq kernel's layout tests (tests/test_gpu_seq_layouts.py): sizes on both sides of every
+    16-row boundary of its lane layout, full tables (32, 64), two J_p entries per row / two column chunks (free b_i), and
+    a sensitivity column without a J_p entry (a parameter no equation refers to, first or last)."""
+    specs = [stiff_spec(n) for n in (16, 17, 24, 31, 32, 33, 48, 49, 64)]
+    specs += [stiff_spec(n, name='stiff%d_free' % n, fixed_deactivation=False) for n in (16, 33, 64)]
+    specs += [stiff_spec(18, name='stiff18_unused_%s' % w, unused=w) for w in ('trailing', 'leading')]
+    return specs
 
 
 def stiff_nominal_params(n=50):

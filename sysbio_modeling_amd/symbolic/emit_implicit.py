@@ -295,9 +295,13 @@ def emit_members(spec, d):
         for i in range(n):
             for q, (_, c) in enumerate(d.jp_rows[i]):
                 col_entries.setdefault(c, []).append((i, q))
-        n_cols = (max(col_entries) + 1) if col_entries else 0
+        # Decided over ALL NK columns: a column without a J_p entry (a parameter no equation refers to) has no row to rotate
+        # round, and a table sized by the last column WITH an entry would be read past its end by the trailing ones.
+        n_cols = spec.n_sens
         rot = chain and n_cols > 0 and all(len(col_entries.get(c, [])) == 1 for c in range(n_cols))
         L += ["  static constexpr bool IM_ROT = %s;" % ("true" if rot else "false"),
+              "  static_assert(!IM_ROT || sizeof(SBM_IM_R0) / sizeof(short) >= NK, \"one rotated-column entry per column\");",
+              "  static_assert(!IM_ROT || sizeof(SBM_IM_JPQ) / sizeof(short) >= NK, \"one rotated-column entry per column\");",
               "  __device__ __forceinline__ static int im_r0(int col) { return SBM_IM_R0[IM_ROT ? col : 0]; }",
               "  __device__ __forceinline__ static int im_jpq(int col) { return SBM_IM_JPQ[IM_ROT ? col : 0]; }"]
         L += emit_distributed(spec, d, pattern, ops)
