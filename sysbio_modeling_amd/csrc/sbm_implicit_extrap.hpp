@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(64) sbm_iex_kernel(sbm_kernel_args a) {
   constexpr int ZS = Sh::ZS;
   __shared__ Sh sh;
   if ((int)blockIdx.x >= a.n_traj) return;
-  const int traj = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
+  const int traj = sbm_traj_of(a, blockIdx.x);
   const int lane = threadIdx.x;
   const int chunk = NCH > 1 ? (int)blockIdx.y : 0;
   const int col = lane + 64 * chunk;
@@ -100,9 +100,7 @@ __global__ void __launch_bounds__(64) sbm_iex_kernel(sbm_kernel_args a) {
   st.setup(&sh, lane, chunk, a.P + (size_t)traj * M::NP);
   __syncthreads();
 
-  const int goff = a.grid_off ? a.grid_off[traj] : 0;
-  const int glen = a.grid_len ? a.grid_len[traj] : a.n_t;
-  const double* tg = a.t_out + goff;
+  const auto [tg, glen] = sbm_grid_window(a, traj);
   const bool with_sens = a.S != nullptr;   // wave-uniform
   double* Yt = a.Y ? a.Y + (size_t)traj * a.n_t * NV : nullptr;
   double* St = a.S ? a.S + (size_t)traj * a.n_t * NV * NK : nullptr;
@@ -136,7 +134,7 @@ __global__ void __launch_bounds__(64) sbm_iex_kernel(sbm_kernel_args a) {
     yn[r] = (a.y0 && st.has_row[r]) ? a.y0[lane + 64 * r] : 0.0;
     ydot[r] = 0.0;                // slope of the last accepted macro step: predictor of a sequence's first Newton iteration
   }
-  Stepper::fence();
+  SBM_LDS_FENCE();
 
   int status = SBM_OK, n_newton = 0;
   long long n_acc = 0, n_rej = 0;
@@ -253,7 +251,7 @@ __global__ void __launch_bounds__(64) sbm_iex_kernel(sbm_kernel_args a) {
         if (with_sens) {
 #pragma unroll
           for (int i = 0; i < NV; ++i) sh.ZN[i * ZS + zl] += zh[i];
-          Stepper::fence();
+          SBM_LDS_FENCE();
         }
         colmax = colmax_new;
         t = landing ? target : t + Hs;
@@ -290,15 +288,7 @@ __global__ void __launch_bounds__(64) sbm_iex_kernel(sbm_kernel_args a) {
     const int na = (int)(n_acc > 2000000000LL ? 2000000000LL : n_acc), nr = (int)(n_rej > 2000000000LL ? 2000000000LL : n_rej);
     // chunks of a trajectory control their steps separately (each carries a copy of the state next to its own
     // columns): worst status, most steps
-    if constexpr (NCH > 1) {
-      if (a.status) atomicMax(a.status + traj, status);
-      if (a.n_steps) atomicMax(a.n_steps + traj, na);
-      if (a.n_reject) atomicMax(a.n_reject + traj, nr);
-    } else {
-      if (a.status) a.status[traj] = status;
-      if (a.n_steps) a.n_steps[traj] = na;
-      if (a.n_reject) a.n_reject[traj] = nr;
-    }
+    sbm_report(a, traj, status, na, nr, NCH > 1);
   }
   (void)n_newton;
 }

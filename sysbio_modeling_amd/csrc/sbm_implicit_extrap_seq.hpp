@@ -136,16 +136,14 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
     if (work >= n_work) break;               // (every wavefront gets here: the counter only grows)
     const int wt = work / nch_launch;
     const int chunk = work - wt * nch_launch;
-    const int traj = a.order ? a.order[wt] : wt;
+    const int traj = sbm_traj_of(a, wt);
     const int col = lane + 64 * chunk;
     const bool has_col = col < NK;
     Stepper st;
     st.setup(&sh, lane, chunk, a.P + (size_t)traj * M::NP);
-    Stepper::fence();
+    SBM_LDS_FENCE();
 
-    const int goff = a.grid_off ? a.grid_off[traj] : 0;
-    const int glen = a.grid_len ? a.grid_len[traj] : a.n_t;
-    const double* tg = a.t_out + goff;
+    const auto [tg, glen] = sbm_grid_window(a, traj);
     double* Yt = a.Y ? a.Y + (size_t)traj * a.n_t * NV : nullptr;
     double* St = a.S ? a.S + (size_t)traj * a.n_t * NV * NK : nullptr;
     const double rtol = a.opts.rtol > 0.0 ? a.opts.rtol : 1e-8, atol = a.opts.atol > 0.0 ? a.opts.atol : 1e-11;
@@ -170,15 +168,12 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
     for (int i = 0; i < NV; ++i) sh.ZN[i * ZS + zl] = (!ROT && a.s0 && has_col) ? a.s0[i * NK + col] : 0.0;
     yn[0] = (a.y0 && st.has_row[0]) ? a.y0[lane] : 0.0;
     ydot[0] = 0.0;
-    Stepper::fence();
+    SBM_LDS_FENCE();
 
     int status = SBM_OK;
     long long n_acc = 0, n_rej = 0;
 #ifdef SBM_SEQ_PROFILE
     long long prof_a = 0, prof_b = 0;
-#if defined(SBM_SEQ_PROFILE2) || defined(SBM_SEQ_PROFILE3) || defined(SBM_SEQ_PROFILE4) || defined(SBM_SEQ_PROFILE5) || defined(SBM_SEQ_PROFILE6) || defined(SBM_SEQ_PROFILE7) || defined(SBM_SEQ_PROFILE8)
-    long long prof_s = 0;
-#endif
     const long long prof_t0 = __builtin_readcyclecounter();
 #endif
     double t = a.opts.t0;
@@ -228,7 +223,7 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
           }
           sh.Y[lane] = yn[0];
           sh.G[lane] = ydot[0];
-          Stepper::fence();
+          SBM_LDS_FENCE();
           // group g runs sequence K - g, then sequence g + 1 (K + 1 Euler steps in all): the harmonic sequence in K / 2 rows
           const bool grp_on = grp < (K + 1) / 2;
           const int j_first = K - grp;
@@ -253,10 +248,6 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
           double ya[RPG], yp[RPG], yp2[RPG], yp3[RPG];
 #pragma unroll
           for (int r = 0; r < RPG; ++r) ya[r] = yp[r] = yp2[r] = yp3[r] = 0.0;
-#ifdef SBM_SEQ_PROFILE7
-          asm volatile("" ::: "memory");
-          prof_s += __builtin_readcyclecounter() - tp0;
-#endif
 #pragma unroll 1
           for (int s = 0; s <= K && rc == SBM_OK; ++s) {
             const bool in_first = s < j_first;
@@ -289,13 +280,9 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
             float r_prev = 0.f;
 #pragma unroll 1
             for (int it = 0;; ++it) {
-#ifdef SBM_SEQ_PROFILE6
-              const long long tq6a = __builtin_readcyclecounter();
-              asm volatile("" ::: "memory");
-#endif
 #pragma unroll
               for (int r = 0; r < RPG; ++r) sh.YG[grp][gl * RPG + r] = yb[r];
-              Stepper::fence();
+              SBM_LDS_FENCE();
               // (ONE straight-line block over the lane's rows: the reciprocals' refinement chains of different rows overlap;
               // the table values wait in registers for the pass in which the group finishes)
               double Ap[RPG], Bp[RPG], tw[LW];
@@ -333,15 +320,6 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
                 for (int q = 0; q < M::RL_MAXJP; ++q) tw[r * W + 2 + q] = jp[q];
               }
               const int mode_in = mode;
-#ifdef SBM_SEQ_PROFILE6
-              asm volatile("" ::: "memory");
-              const long long tq6 = __builtin_readcyclecounter();
-              prof_s += tq6 - tq6a;
-#endif
-#ifdef SBM_SEQ_PROFILE8
-              const long long tq8 = __builtin_readcyclecounter();
-              asm volatile("" ::: "memory");
-#endif
               if (__builtin_amdgcn_ballot_w64(mode == MODE_ITER) == 0ull) {
                 // every group still at work only wanted its matrices at the converged state: no update, no test
                 if (with_sens && mode == MODE_FINAL) {
@@ -399,10 +377,6 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
                 // the group has finished this Euler step: tw holds the matrices of its last evaluation
                 store_table(trow, tw);
               }
-#ifdef SBM_SEQ_PROFILE8
-              asm volatile("" ::: "memory");
-              prof_s += __builtin_readcyclecounter() - tq8;
-#endif
               if (__builtin_amdgcn_ballot_w64(bad) != 0ull) { rc = SBM_NON_FINITE; break; }
               if (__builtin_amdgcn_ballot_w64(mode != MODE_DONE) == 0ull) break;
               if (it >= 8) { rc = SBM_NEWTON_FAIL; break; }      // eight updates, as newton_rate<8>
@@ -418,14 +392,14 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
           }
           if (rc == SBM_OK) {
             // the two extrapolations on the row lanes
-            Stepper::fence();
+            SBM_LDS_FENCE();
 #pragma unroll 1
             for (int j = 1; j <= K; ++j) {
               const double d = sh.TG[j - 1][lane] - yn[0];
               yh[0] = fma(SBM_IEX_W.wh[K][j], d, yh[0]);
               ye[0] = fma(SBM_IEX_W.we[K][j], d, ye[0]);
             }
-            Stepper::fence();
+            SBM_LDS_FENCE();
           }
         }
 
@@ -479,35 +453,15 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
 #pragma unroll 1
           for (int kstep = 0; kstep < n_euler; ++kstep) {
             if (m == 0) {
-#ifdef SBM_SEQ_PROFILE5
-              const long long tq5 = __builtin_readcyclecounter();
-              asm volatile("" ::: "memory");
-#endif
 #pragma unroll
               for (int i = 0; i < NV; ++i) zs[i] = sh.ZN[i * ZS + zl];
               h = Hs * sbm_iex_rj(j);
-#ifdef SBM_SEQ_PROFILE5
-              asm volatile("" ::: "memory");
-              prof_s += __builtin_readcyclecounter() - tq5;
-#endif
             }
-#ifdef SBM_SEQ_PROFILE4
-            const long long tq4 = __builtin_readcyclecounter();
-            asm volatile("" ::: "memory");
-#endif
             issue(kstep + NR - 1);
             asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * (NR - 1)) : "memory");
-#ifdef SBM_SEQ_PROFILE4
-            asm volatile("" ::: "memory");
-            prof_s += __builtin_readcyclecounter() - tq4;
-#endif
             const double* const ent = &sh.RING[(kstep % NR) * ENTRY];
             const double2* const rt = reinterpret_cast<const double2*>(ent) + r0;
             const double ha = (h * colmask) * ent[128 + (r0 & 63)];       // (no branch round the read: idle lanes multiply by zero)
-#ifdef SBM_SEQ_PROFILE2
-            const long long tq0 = __builtin_readcyclecounter();
-            asm volatile("" ::: "memory");
-#endif
             // blocks of BK rows, coefficients two blocks ahead of the arithmetic
             constexpr int BK = 5, NB = (NV + BK - 1) / BK;
             // (a block's rows are read LAST ROW FIRST: LDS answers in order, so the wait for the block's first row -- the last
@@ -518,15 +472,15 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
             for (int b = 0; b < 2 && b < NB; ++b) {
 #pragma unroll
               for (int e = BK - 1; e >= 0; --e) tb[b][e] = rt[(b * BK + e) < NV ? b * BK + e : 0];
-              Stepper::fence();
+              SBM_LDS_FENCE();
             }
             sbm_static_for<NB>([&](auto bc) {
               constexpr int b = decltype(bc)::value;
-              Stepper::fence();
+              SBM_LDS_FENCE();
               if constexpr (b + 2 < NB) {
 #pragma unroll
                 for (int e = BK - 1; e >= 0; --e) tb[(b + 2) % 3][e] = rt[((b + 2) * BK + e) < NV ? (b + 2) * BK + e : 0];
-                Stepper::fence();
+                SBM_LDS_FENCE();
               }
 #pragma unroll
               for (int e = 0; e < BK; ++e) {
@@ -538,16 +492,8 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
                 }
               }
             });
-            Stepper::fence();
-#ifdef SBM_SEQ_PROFILE2
-            asm volatile("" ::: "memory");
-            prof_s += __builtin_readcyclecounter() - tq0;
-#endif
+            SBM_LDS_FENCE();
             if (++m == j) {
-#ifdef SBM_SEQ_PROFILE3
-              const long long tq1 = __builtin_readcyclecounter();
-              asm volatile("" ::: "memory");
-#endif
               const double wh = SBM_IEX_W.wh[K][j], we = SBM_IEX_W.we[K][j];
 #pragma unroll
               for (int i = 0; i < NV; ++i) {
@@ -556,10 +502,6 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
               }
               m = 0;
               ++j;
-#ifdef SBM_SEQ_PROFILE3
-              asm volatile("" ::: "memory");
-              prof_s += __builtin_readcyclecounter() - tq1;
-#endif
             }
           }
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the ring's last (clamped) loads
@@ -601,7 +543,7 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
 #pragma unroll
                   for (int q = 0; q < M::RL_MAXJP; ++q) sh.A[st.apos[0][q]] = wn[p][2 + q];
                 }
-                Stepper::fence();
+                SBM_LDS_FENCE();
                 {
                   const int kn = kstep + PF < Pl::NSTEP ? kstep + PF : Pl::NSTEP - 1;
                   const double* src = src0 + (size_t)kn * Pl::STEP_DOUBLES;
@@ -609,16 +551,8 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
                   for (int q = 0; q < W; ++q) wn[p][q] = src[q];
                 }
 #endif
-#ifdef SBM_SEQ_PROFILE2
-                const long long tq0 = __builtin_readcyclecounter();
-                asm volatile("" ::: "memory");
-#endif
 #ifndef SBM_SEQ_NO_SENS
                 st.sens_euler(h, zs);
-#endif
-#ifdef SBM_SEQ_PROFILE2
-                asm volatile("" ::: "memory");
-                prof_s += __builtin_readcyclecounter() - tq0;
 #endif
                 if (++m == j) {
                   // zh = sum_j wH_j T_j = T_KK itself (the weights add up to one), ze = sum_j (wH_j - wL_j) T_j (they add up to
@@ -676,7 +610,7 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
           if (with_sens) {
 #pragma unroll
             for (int i = 0; i < NV; ++i) sh.ZN[i * ZS + zl] = zh[i];
-            Stepper::fence();
+            SBM_LDS_FENCE();
           }
           colmax = colmax_new;
           t = landing ? target : t + Hs;
@@ -708,23 +642,12 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
 #ifdef SBM_SEQ_PROFILE      // developer build: kilocycles of phase A in n_steps, of phase B in n_reject, of the trajectory in status
     n_acc = prof_a >> 10;
     n_rej = prof_b >> 10;
-#if defined(SBM_SEQ_PROFILE2) || defined(SBM_SEQ_PROFILE3) || defined(SBM_SEQ_PROFILE4) || defined(SBM_SEQ_PROFILE5) || defined(SBM_SEQ_PROFILE6) || defined(SBM_SEQ_PROFILE7) || defined(SBM_SEQ_PROFILE8)
-    n_acc = prof_s >> 10;      // the column step (2) / the accumulation (3) alone instead of phase A
-#endif
     status = (int)((__builtin_readcyclecounter() - prof_t0) >> 10);
 #endif
     if (lane == 0) {
       const int na = (int)(n_acc > 2000000000LL ? 2000000000LL : n_acc), nr = (int)(n_rej > 2000000000LL ? 2000000000LL : n_rej);
-      if (nch_launch > 1) {
-        if (a.status) atomicMax(a.status + traj, status);
-        if (a.n_steps) atomicMax(a.n_steps + traj, na);
-        if (a.n_reject) atomicMax(a.n_reject + traj, nr);
-      } else {
-        if (a.status) a.status[traj] = status;
-        if (a.n_steps) a.n_steps[traj] = na;
-        if (a.n_reject) a.n_reject[traj] = nr;
-      }
+      sbm_report(a, traj, status, na, nr, nch_launch > 1);
     }
-    Stepper::fence();
+    SBM_LDS_FENCE();
   }
 }

@@ -94,8 +94,6 @@ struct SbmImplicitStepper {
   static constexpr bool CHAIN = M::IM_CHAIN && RPL == 1 && !DIST;
   double ch_a, ch_b;                               // CHAIN: this lane's row of the recurrence x_i = b_i + a_i x_{i-1}
 
-  __device__ __forceinline__ static void fence() { __atomic_signal_fence(__ATOMIC_SEQ_CST); }
-
   // Clears the LDS tables and loads this lane's rows (operand indices, parameters, output positions).  `chunk` = which
   // 64 columns of S this wavefront advances.  The caller synchronises (one wavefront per block: a fence suffices).
   __device__ __forceinline__ void setup(Sh* shared, int lane_, int chunk_, const double* P) {
@@ -163,26 +161,26 @@ struct SbmImplicitStepper {
       // the table still holds the previous factors: clear the row (16-byte stores), then scatter the entries of M
 #pragma unroll
       for (int j = 0; j + 1 < LD; j += 2) *reinterpret_cast<double2*>(myrow + j) = double2{0.0, 0.0};
-      fence();
+      SBM_LDS_FENCE();
       myrow[lane] = 1.0;
     }
-    fence();
+    SBM_LDS_FENCE();
 #pragma unroll
     for (int q = 0; q < M::RL_MAXJY; ++q) {
       const double v = -hh * jy[q];
       sh->MF[mfpos[0][q]] = diagslot[0] == q ? 1.0 + v : v;
     }
-    fence();
+    SBM_LDS_FENCE();
     double row[NV];
 #pragma unroll
     for (int j = 0; j < NV; ++j) row[j] = myrow[j];
-    fence();
+    SBM_LDS_FENCE();
     M::im_factor_rows(row, lane, sh->RD);
     if (has_row[0]) {
 #pragma unroll
       for (int j = 0; j < NV; ++j) myrow[j] = row[j];
     }
-    fence();
+    SBM_LDS_FENCE();
   }
 
   // Newton on the midpoint state of one step of size 2*hh from y: on entry yb = predictor, on exit the midpoint.
@@ -219,7 +217,7 @@ struct SbmImplicitStepper {
   __device__ __forceinline__ void eval_factor(double tm, double hh, const double (&y)[RPL], const double (&yb)[RPL]) {
 #pragma unroll
     for (int r = 0; r < RPL; ++r) sh->Y[lane + 64 * r] = yb[r];
-    fence();
+    SBM_LDS_FENCE();
 #pragma unroll
     for (int r = 0; r < RPL; ++r) {
       double ys[M::RL_MAXYS];
@@ -231,7 +229,7 @@ struct SbmImplicitStepper {
 #pragma unroll
       for (int q = 0; q < M::RL_MAXJP; ++q) jp[q] = 0.0;
       M::class_dispatch(cls[r], tm, ys, ps[r], f, jy, jp);
-      fence();
+      SBM_LDS_FENCE();
 #pragma unroll
       for (int q = 0; q < M::RL_MAXJP; ++q) sh->A[apos[r][q]] = jp[q];
       if constexpr (!M::IM_TRI && !DIST) {
@@ -258,7 +256,7 @@ struct SbmImplicitStepper {
         factor_rows(hh, jy);
       }
     }
-    fence();
+    SBM_LDS_FENCE();
     if constexpr (!M::IM_TRI && !DIST) {
       M::im_build(hh, sh->JY, m);
       M::im_factor(m);
@@ -314,14 +312,14 @@ struct SbmImplicitStepper {
       int lo = lane;               // (opaque: the 2 NV lane masks are otherwise hoisted out of every loop and spilled)
       asm volatile("" : "+v"(lo));
       M::template im_solve_tri_pick<RPL>(sh->MF, sh->G, lo, d);
-      fence();
+      SBM_LDS_FENCE();
     } else {
       double b[NV];
 #pragma unroll
       for (int i = 0; i < NV; ++i) b[i] = sh->G[i];
       if constexpr (DIST) M::im_solve_lds(sh->MF, sh->RD, b);
       else M::im_solve(m, b);
-      fence();
+      SBM_LDS_FENCE();
       sbm_static_for<RPL>([&](auto rc) {
         constexpr int r = decltype(rc)::value;
         constexpr int CNT = (NV - 64 * r) < 64 ? (NV - 64 * r) : 64;
@@ -404,7 +402,7 @@ struct SbmImplicitStepper {
     if constexpr (DIST) M::im_solve_lds(sh->MF, sh->RD, b);
     else if constexpr (M::IM_TRI) M::im_solve_tri(sh->MF, b);
     else M::im_solve(m, b);
-    fence();
+    SBM_LDS_FENCE();
 #pragma unroll
     for (int i = 0; i < NV; ++i) z[i] = fma(2.0, b[i], -z[i]);
   }
@@ -417,7 +415,7 @@ struct SbmImplicitStepper {
       int lo = lane + 64 * chunk;  // (opaque: see solve_delta)
       asm volatile("" : "+v"(lo));
       M::im_sens_tri(sh->MF, sh->A, hh, lo, z);
-      fence();
+      SBM_LDS_FENCE();
       return;
     } else if constexpr (Sh::A_SPARSE) {
       int lo = lane + 64 * chunk;  // (opaque: see solve_delta)
@@ -436,6 +434,6 @@ struct SbmImplicitStepper {
     if constexpr (DIST) M::im_solve_lds(sh->MF, sh->RD, z);
     else if constexpr (M::IM_TRI) M::im_solve_tri(sh->MF, z);
     else M::im_solve(m, z);
-    fence();
+    SBM_LDS_FENCE();
   }
 };

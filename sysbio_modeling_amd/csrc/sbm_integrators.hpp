@@ -221,9 +221,22 @@ struct SbmLdsParams {  // [param][lane] image in LDS
   __device__ __forceinline__ double operator[](int c) const { return base[c * 64]; }
 };
 
+// Systems WITHOUT a row phase (everything happens in rhs): the stage phases of the drivers collapse to finish = rhs.
+template <class D>
+struct SbmNoRowPhase {
+  struct Pending {};
+  template <class Z>
+  __device__ __forceinline__ Pending issue(double, const Z&) const { return Pending{}; }
+  __device__ __forceinline__ int eval(const Pending&, double) const { return 0; }
+  template <class Z>
+  __device__ __forceinline__ void extra_out(int, Z&) const {}
+  template <class Z>
+  __device__ __forceinline__ void finish(int, double t, const Z& z, Z& dz) const { static_cast<const D*>(this)->rhs(t, z, dz); }
+};
+
 // one trajectory per wave; lane = column of [y | S]
 template <class M>
-struct SensSystem {
+struct SensSystem : SbmNoRowPhase<SensSystem<M>> {
   static constexpr int NV = M::NV;
   static constexpr int NVX = M::NV;   // no extra per-lane elements
   static constexpr int NCOL = 1 + M::NK;
@@ -260,18 +273,11 @@ struct SensSystem {
     return sqrtf(sbm_wave_max(m) * (1.0f / NV));   // +inf: the driver rejects the step
   }
   __device__ __forceinline__ double sum(double v) const { return sbm_wave_sum(v); }
-  struct Pending {};
-  __device__ __forceinline__ Pending issue(double, const double (&)[CPL][NV]) const { return Pending{}; }
-  __device__ __forceinline__ int eval(const Pending&, double) const { return 0; }
-  __device__ __forceinline__ void extra_out(int, double (&)[CPL][NV]) const {}
-  __device__ __forceinline__ void finish(int, double t, const double (&z)[CPL][NV], double (&dz)[CPL][NV]) const {
-    rhs(t, z, dz);
-  }
 };
 
 // one trajectory per lane; state only
 template <class M>
-struct StateSystem {
+struct StateSystem : SbmNoRowPhase<StateSystem<M>> {
   static constexpr int NV = M::NV;
   static constexpr int NVX = M::NV;
   static constexpr int CPL = 1;
@@ -287,13 +293,6 @@ struct StateSystem {
     return sqrtf(colsum[0] * (1.0f / NV));
   }
   __device__ __forceinline__ double sum(double v) const { return v; }
-  struct Pending {};
-  __device__ __forceinline__ Pending issue(double, const double (&)[1][NV]) const { return Pending{}; }
-  __device__ __forceinline__ int eval(const Pending&, double) const { return 0; }
-  __device__ __forceinline__ void extra_out(int, double (&)[1][NV]) const {}
-  __device__ __forceinline__ void finish(int, double t, const double (&z)[1][NV], double (&dz)[1][NV]) const {
-    rhs(t, z, dz);
-  }
 };
 
 // ---------------------------------------------------------------------------
@@ -304,6 +303,34 @@ struct SbmTrajOut {
   int32_t n_acc;
   int32_t n_rej;
 };
+
+// ---- what every kernel does before and after its trajectory ----
+// the trajectory of workgroup / work item `block`: the caller's order (longest first) or the index itself; wave-uniform
+template <class I>
+__device__ __forceinline__ int sbm_traj_of(const sbm_kernel_args& a, I block) { return a.order ? a.order[block] : (int)block; }
+// the trajectory's window of the shared time grid
+struct SbmGridWindow {
+  const double* t;
+  int n;
+};
+__device__ __forceinline__ SbmGridWindow sbm_grid_window(const sbm_kernel_args& a, int traj) {
+  const int goff = a.grid_off ? a.grid_off[traj] : 0;
+  const int glen = a.grid_len ? a.grid_len[traj] : a.n_t;
+  return SbmGridWindow{a.t_out + goff, glen};
+}
+// Called by the one lane that reports.  merge: several wavefronts (column chunks) share the trajectory -- worst status,
+// most steps over the chunks (all non-negative; zeroed by the launcher).
+__device__ __forceinline__ void sbm_report(const sbm_kernel_args& a, int traj, int status, int n_acc, int n_rej, bool merge) {
+  if (merge) {
+    if (a.status) atomicMax(a.status + traj, status);
+    if (a.n_steps) atomicMax(a.n_steps + traj, n_acc);
+    if (a.n_reject) atomicMax(a.n_reject + traj, n_rej);
+  } else {
+    if (a.status) a.status[traj] = status;
+    if (a.n_steps) a.n_steps[traj] = n_acc;
+    if (a.n_reject) a.n_reject[traj] = n_rej;
+  }
+}
 
 // Dormand-Prince 5(4) with FSAL, I-controller (safety 0.9, factor in [0.2, 10]),
 // landing exactly on every output time (the reference samples the solution AT
@@ -787,13 +814,11 @@ __global__ void __launch_bounds__(64) sbm_sens_kernel(sbm_kernel_args a) {
   constexpr int CPL = Sys::CPL;
   constexpr int NK = M::NK;
   if ((int)blockIdx.x >= a.n_traj) return;
-  const int traj = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;  // wave-uniform
+  const int traj = sbm_traj_of(a, blockIdx.x);  // wave-uniform
   const int lane = threadIdx.x;
 
-  Sys sys{a.P + (size_t)traj * M::NP, lane};
-  const int goff = a.grid_off ? a.grid_off[traj] : 0;
-  const int glen = a.grid_len ? a.grid_len[traj] : a.n_t;
-  const double* tg = a.t_out + goff;
+  Sys sys{{}, a.P + (size_t)traj * M::NP, lane};
+  const auto [tg, glen] = sbm_grid_window(a, traj);
 
   double z[CPL][NV];
 #pragma unroll
@@ -830,13 +855,8 @@ __global__ void __launch_bounds__(64) sbm_sens_kernel(sbm_kernel_args a) {
     }
   };
 
-  SbmTrajOut r = sbm_integrate<METHOD>(sys, z, tg, glen, a.opts, store);
-
-  if (lane == 0) {
-    if (a.status) a.status[traj] = r.status;
-    if (a.n_steps) a.n_steps[traj] = r.n_acc;
-    if (a.n_reject) a.n_reject[traj] = r.n_rej;
-  }
+  const SbmTrajOut r = sbm_integrate<METHOD>(sys, z, tg, glen, a.opts, store);
+  if (lane == 0) sbm_report(a, traj, r.status, r.n_acc, r.n_rej, false);
 }
 
 // State-only kernel.  One trajectory per lane, 64 per block.
@@ -860,7 +880,7 @@ __global__ void __launch_bounds__(64) sbm_state_kernel(sbm_kernel_args a) {
   __syncthreads();
   if (traj >= a.n_traj) return;
 
-  Sys sys{SbmLdsParams{p_lds + lane}};
+  Sys sys{{}, SbmLdsParams{p_lds + lane}};
   const int goff = a.grid_off ? a.grid_off[traj] : 0;
   const int glen = a.grid_len ? a.grid_len[traj] : a.n_t;
   const double* tg = a.t_out + goff;
@@ -928,9 +948,7 @@ struct RowLaneSystem {
 
   // LDS traffic of ONE wave is processed in issue order, so a ds_read issued after a ds_write of
   // another lane sees that write: no barrier and no waitcnt is needed between the phases below,
-  // only a compiler-level fence that keeps the memory operations in program order.
-  __device__ __forceinline__ static void lds_order() { __atomic_signal_fence(__ATOMIC_SEQ_CST); }
-
+  // only a compiler-level fence (SBM_LDS_FENCE) that keeps the memory operations in program order.
   struct Token {
     double f;                  // derivative of this lane's state component
     double jy[M::RL_MAXJY];    // J_y entries of this lane's row (read by the other lanes via v_readlane)
@@ -940,10 +958,10 @@ struct RowLaneSystem {
   __device__ __forceinline__ Pending issue(double /*t*/, const double (&z)[1][NVX]) const {
     Pending p;
     sh->Y[lane] = z[0][NV];
-    lds_order();
+    SBM_LDS_FENCE();
 #pragma unroll
     for (int s = 0; s < M::RL_MAXYS; ++s) p.ys[s] = sh->Y[yidx[s]];
-    lds_order();
+    SBM_LDS_FENCE();
     return p;
   }
   // eval: evaluate the lane's row and publish its J_p entries
@@ -957,10 +975,10 @@ struct RowLaneSystem {
     for (int s = 0; s < M::RL_MAXJP; ++s) jp[s] = 0.0;
     M::class_dispatch(cls, t, p.ys, ps, k.f, k.jy, jp);
     k.f = cls >= 0 ? k.f : 0.0;   // lanes without a row come out of the select chain with the last class's value
-    lds_order();
+    SBM_LDS_FENCE();
 #pragma unroll
     for (int s = 0; s < M::RL_MAXJP; ++s) sh->A[apos[s]] = jp[s];
-    lds_order();
+    SBM_LDS_FENCE();
     return k;
   }
   // phase 2: the lane's column, dz = J_y z + A[:, lane]
@@ -974,7 +992,7 @@ struct RowLaneSystem {
     double acol[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) acol[i] = sh->A[i * 64 + lane];
-    lds_order();
+    SBM_LDS_FENCE();
     M::apply_rowlane(k.jy, sj, acol, zc, dc);
 #pragma unroll
     for (int i = 0; i < NV; ++i) dz[0][i] = dc[i];
@@ -1007,7 +1025,7 @@ __global__ void __launch_bounds__(64) sbm_sens_rowlane_kernel(sbm_kernel_args a)
   static_assert(NV <= 64 && NK <= 64, "row-lane kernel: one row and one column per lane");
   __shared__ SbmRowLaneShared<M> sh;
   if ((int)blockIdx.x >= a.n_traj) return;
-  const int traj = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
+  const int traj = sbm_traj_of(a, blockIdx.x);
   const int lane = threadIdx.x;
 
   for (int i = lane; i < NV * 64 + 2; i += 64) sh.A[i] = 0.0;
@@ -1039,9 +1057,7 @@ __global__ void __launch_bounds__(64) sbm_sens_rowlane_kernel(sbm_kernel_args a)
     M::rl_static(jy0, sys.sj);
   }
 
-  const int goff = a.grid_off ? a.grid_off[traj] : 0;
-  const int glen = a.grid_len ? a.grid_len[traj] : a.n_t;
-  const double* tg = a.t_out + goff;
+  const auto [tg, glen] = sbm_grid_window(a, traj);
 
   double z[1][NVX];
 #pragma unroll
@@ -1058,15 +1074,8 @@ __global__ void __launch_bounds__(64) sbm_sens_rowlane_kernel(sbm_kernel_args a)
     }
   };
 
-  SbmTrajOut r;
-  r = sbm_integrate<METHOD>(sys, z, tg, glen, a.opts, store);
-
-
-  if (lane == 0) {
-    if (a.status) a.status[traj] = r.status;
-    if (a.n_steps) a.n_steps[traj] = r.n_acc;
-    if (a.n_reject) a.n_reject[traj] = r.n_rej;
-  }
+  const SbmTrajOut r = sbm_integrate<METHOD>(sys, z, tg, glen, a.opts, store);
+  if (lane == 0) sbm_report(a, traj, r.status, r.n_acc, r.n_rej, false);
 }
 
 // ===========================================================================
@@ -1099,12 +1108,12 @@ struct StateRowSystem {
     Pending p;
 #pragma unroll
     for (int r = 0; r < RPL; ++r) Y[lane + 64 * r] = z[0][r];
-    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    SBM_LDS_FENCE();
 #pragma unroll
     for (int r = 0; r < RPL; ++r)
 #pragma unroll
       for (int s = 0; s < M::RL_MAXYS; ++s) p.ys[r][s] = Y[yidx[r][s]];
-    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    SBM_LDS_FENCE();
     return p;
   }
   __device__ __forceinline__ Token eval(const Pending& p, double t) const {
@@ -1172,9 +1181,7 @@ __global__ void __launch_bounds__(64) sbm_state_rows_kernel(sbm_kernel_args a) {
     for (int r = 0; r < RPL; ++r)
       if (lane + 64 * r < M::NV) Yt[(size_t)io * M::NV + lane + 64 * r] = zz[0][r];
   };
-  SbmTrajOut r;
-  r = sbm_integrate<METHOD>(sys, z, tg, glen, a.opts, store);
-
+  const SbmTrajOut r = sbm_integrate<METHOD>(sys, z, tg, glen, a.opts, store);
   if (lane == 0) {
     if (a.status) a.status[traj] = r.status;
     if (a.n_steps) a.n_steps[traj] = r.n_acc;
@@ -1201,12 +1208,13 @@ __global__ void __launch_bounds__(64) sbm_state_rows_kernel(sbm_kernel_args a) {
 // reduction whose lanes add the same numbers in different orders).  Every level is an exchange between two lanes that
 // both form own + other -- commutative, hence identical: quad_perm (xor 1, xor 2), row_half_mirror (i <-> 7 - i),
 // row_mirror (i <-> 15 - i) on DPP, the two rows of a 32-lane segment through ds_bpermute.
+// (SEG 4 and 8 -- the levels guarded by SEG >= 8 / >= 16 -- serve sbm_sens_packed_kernel further down, next to sbm_seg_maxf_any)
 template <int SEG>
-__device__ __forceinline__ float sbm_seg_sumf(float v) {
-  v += sbm_dpp<0xb1, 0xf>(v);    // quad_perm:[1,0,3,2]
-  v += sbm_dpp<0x4e, 0xf>(v);    // quad_perm:[2,3,0,1]
-  v += sbm_dpp<0x141, 0xf>(v);   // row_half_mirror
-  v += sbm_dpp<0x140, 0xf>(v);   // row_mirror: every lane of the row of 16 holds the row's sum
+__device__ __forceinline__ float sbm_seg_sumf_any(float v) {
+  v += sbm_dpp<0xb1, 0xf>(v);                              // quad_perm:[1,0,3,2]
+  v += sbm_dpp<0x4e, 0xf>(v);                              // quad_perm:[2,3,0,1]
+  if constexpr (SEG >= 8) v += sbm_dpp<0x141, 0xf>(v);     // row_half_mirror
+  if constexpr (SEG >= 16) v += sbm_dpp<0x140, 0xf>(v);    // row_mirror: every lane of the row of 16 holds the row's sum
   if constexpr (SEG == 32) v += __shfl_xor(v, 16, 64);
   return v;
 }
@@ -1237,10 +1245,10 @@ struct PackedStateRowSystem {
   __device__ __forceinline__ Pending issue(double, const double (&z)[1][1]) const {
     Pending p;
     Y[lane] = z[0][0];
-    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    SBM_LDS_FENCE();
 #pragma unroll
     for (int s = 0; s < M::RL_MAXYS; ++s) p.ys[s] = Y[yidx[s]];
-    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    SBM_LDS_FENCE();
     return p;
   }
   __device__ __forceinline__ Token eval(const Pending& p, double t) const {
@@ -1264,7 +1272,7 @@ struct PackedStateRowSystem {
   __device__ __forceinline__ float norm(const float (&)[1], float xsum) const {
     static_assert(kDpp, "segment reductions: widths 16 and 32");
     const float x = has_row ? sbm_nan_to_inf(xsum) : 0.f;
-    return sqrtf(sbm_seg_sumf<SEG>(x) * (1.0f / M::NV));
+    return sqrtf(sbm_seg_sumf_any<SEG>(x) * (1.0f / M::NV));
   }
   __device__ __forceinline__ double sum(double v) const {
     static_assert(kDpp, "segment reductions: widths 16 and 32");
@@ -1297,23 +1305,15 @@ __global__ void __launch_bounds__(64) sbm_state_packed_kernel(sbm_kernel_args a)
 #pragma unroll
   for (int s = 0; s < M::RL_MAXPS; ++s) sys.ps[s] = P[M::rl_ps(s, row)];
   __syncthreads();
-  const int goff = a.grid_off ? a.grid_off[traj] : 0;
-  const int glen = a.grid_len ? a.grid_len[traj] : a.n_t;
-  const double* tg = a.t_out + goff;
+  const auto [tg, glen] = sbm_grid_window(a, traj);
   double z[1][1];
   z[0][0] = (a.y0 && sys.has_row) ? a.y0[li] : 0.0;
   double* Yt = a.Y + (size_t)traj * a.n_t * M::NV;
   auto store = [&](int io, const double (&zz)[1][1]) {
     if (sys.has_row && live) Yt[(size_t)io * M::NV + li] = zz[0][0];
   };
-  SbmTrajOut r;
-  r = sbm_integrate<METHOD>(sys, z, tg, glen, a.opts, store);
-
-  if (li == 0 && live) {
-    if (a.status) a.status[traj] = r.status;
-    if (a.n_steps) a.n_steps[traj] = r.n_acc;
-    if (a.n_reject) a.n_reject[traj] = r.n_rej;
-  }
+  const SbmTrajOut r = sbm_integrate<METHOD>(sys, z, tg, glen, a.opts, store);
+  if (li == 0 && live) sbm_report(a, traj, r.status, r.n_acc, r.n_rej, false);
 }
 
 // ===========================================================================
@@ -1387,8 +1387,6 @@ struct RowGroupSystem {
   double* h_lane;
   int hoff[NH];
 
-  __device__ __forceinline__ static void lds_order() { __atomic_signal_fence(__ATOMIC_SEQ_CST); }
-
   struct Token {
     double f[RPL];
     double acol[EARLY ? NV : 1], coef[EARLY ? RPG * L::RG_JYS : 1];
@@ -1398,12 +1396,12 @@ struct RowGroupSystem {
     Pending p;
 #pragma unroll
     for (int r = 0; r < RPL; ++r) sh->Y[lane + 64 * r] = z[0][NV + r];
-    lds_order();
+    SBM_LDS_FENCE();
 #pragma unroll
     for (int r = 0; r < RPL; ++r)
 #pragma unroll
       for (int s = 0; s < M::RL_MAXYS; ++s) p.ys[r][s] = sh->Y[yidx[r][s]];
-    lds_order();
+    SBM_LDS_FENCE();
     return p;
   }
   __device__ __forceinline__ Token eval(const Pending& p, double t) const {
@@ -1419,7 +1417,7 @@ struct RowGroupSystem {
       M::class_dispatch(cls[r], t, p.ys[r], ps[r], k.f[r], jy[r], jp[r]);
       k.f[r] = cls[r] >= 0 ? k.f[r] : 0.0;   // lanes without a row come out of the select chain with the last class's value
     }
-    lds_order();
+    SBM_LDS_FENCE();
 #pragma unroll
     for (int r = 0; r < RPL; ++r) {
 #pragma unroll
@@ -1427,10 +1425,10 @@ struct RowGroupSystem {
 #pragma unroll
       for (int s = 0; s < M::RL_MAXJY; ++s) sh->JYL[jypos[r][s]] = jy[r][s];
     }
-    lds_order();
+    SBM_LDS_FENCE();
     if constexpr (EARLY) {
       L::load_rowgroup(a_lane, jy_lane, k.acol, k.coef);
-      lds_order();
+      SBM_LDS_FENCE();
     }
     return k;
   }
@@ -1440,7 +1438,7 @@ struct RowGroupSystem {
 #pragma unroll
     for (int i = 0; i < NV; ++i) zc[i] = z[0][i];
     L::publish_rowgroup(h_lane, zc);
-    lds_order();
+    SBM_LDS_FENCE();
     if constexpr (EARLY) {
       L::apply_rowgroup(k.acol, k.coef, sh->H, hoff, zc, dc);
     } else {
@@ -1448,7 +1446,7 @@ struct RowGroupSystem {
       L::load_rowgroup(a_lane, jy_lane, acol, coef);
       L::apply_rowgroup(acol, coef, sh->H, hoff, zc, dc);
     }
-    lds_order();
+    SBM_LDS_FENCE();
 #pragma unroll
     for (int i = 0; i < NV; ++i) dz[0][i] = dc[i];
   }
@@ -1505,7 +1503,7 @@ __global__ void __launch_bounds__(64, SBM_RG_MIN_WAVES) sbm_sens_rowgroup_kernel
   static_assert(G * C <= 64 && C * CPL * NCH >= NK && C * CPL * (NCH - 1) < NK && NPAD >= MNV, "row-group layout");
   __shared__ Sh sh;
   if ((int)blockIdx.x >= a.n_traj) return;
-  const int traj = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
+  const int traj = sbm_traj_of(a, blockIdx.x);
   const int lane = threadIdx.x;
   const int chunk = NCH > 1 ? (int)blockIdx.y : 0;
   const int cbase = chunk * (C * CPL);
@@ -1561,9 +1559,7 @@ __global__ void __launch_bounds__(64, SBM_RG_MIN_WAVES) sbm_sens_rowgroup_kernel
   }
   __syncthreads();
 
-  const int goff = a.grid_off ? a.grid_off[traj] : 0;
-  const int glen = a.grid_len ? a.grid_len[traj] : a.n_t;
-  const double* tg = a.t_out + goff;
+  const auto [tg, glen] = sbm_grid_window(a, traj);
 
   // element (r, cc) of this lane = S[grp*RPG + r][cp + C*cc]
   double z[1][NVX];
@@ -1597,22 +1593,8 @@ __global__ void __launch_bounds__(64, SBM_RG_MIN_WAVES) sbm_sens_rowgroup_kernel
     }
   };
 
-  SbmTrajOut r;
-  r = sbm_integrate<METHOD>(sys, z, tg, glen, a.opts, store);
-
-
-  if (lane == 0) {
-    if constexpr (NCH > 1) {
-      // worst status, most steps over the chunks (all non-negative; zeroed by the launcher)
-      if (a.status) atomicMax(a.status + traj, r.status);
-      if (a.n_steps) atomicMax(a.n_steps + traj, r.n_acc);
-      if (a.n_reject) atomicMax(a.n_reject + traj, r.n_rej);
-    } else {
-      if (a.status) a.status[traj] = r.status;
-      if (a.n_steps) a.n_steps[traj] = r.n_acc;
-      if (a.n_reject) a.n_reject[traj] = r.n_rej;
-    }
-  }
+  const SbmTrajOut r = sbm_integrate<METHOD>(sys, z, tg, glen, a.opts, store);
+  if (lane == 0) sbm_report(a, traj, r.status, r.n_acc, r.n_rej, NCH > 1);
 }
 
 // ===========================================================================
@@ -1630,15 +1612,6 @@ __global__ void __launch_bounds__(64, SBM_RG_MIN_WAVES) sbm_sens_rowgroup_kernel
 // depend on which trajectories share its wavefront (tested bitwise).  Used from 2048 trajectories on
 // (SBM_VARIANT_PACKED forces it).
 // ===========================================================================
-template <int SEG>
-__device__ __forceinline__ float sbm_seg_sumf_any(float v) {
-  v += sbm_dpp<0xb1, 0xf>(v);                              // quad_perm:[1,0,3,2]
-  v += sbm_dpp<0x4e, 0xf>(v);                              // quad_perm:[2,3,0,1]
-  if constexpr (SEG >= 8) v += sbm_dpp<0x141, 0xf>(v);     // row_half_mirror
-  if constexpr (SEG >= 16) v += sbm_dpp<0x140, 0xf>(v);    // row_mirror
-  if constexpr (SEG == 32) v += __shfl_xor(v, 16, 64);
-  return v;
-}
 template <int SEG>
 __device__ __forceinline__ float sbm_seg_maxf_any(float v) {
   v = fmaxf(v, sbm_dpp<0xb1, 0xf>(v));
@@ -1673,16 +1646,15 @@ struct PackedRowLaneSystem {
   const double* jyl;        // this segment's J_y table
   const double* acolp;      // this lane's column of the segment's A: acolp[i * SEG]
 
-  __device__ __forceinline__ static void lds_order() { __atomic_signal_fence(__ATOMIC_SEQ_CST); }
   struct Token { double f; };
   struct Pending { double ys[M::RL_MAXYS]; };
   __device__ __forceinline__ Pending issue(double, const double (&z)[1][NVX]) const {
     Pending p;
     sh->Y[lane] = z[0][NV];
-    lds_order();
+    SBM_LDS_FENCE();
 #pragma unroll
     for (int s = 0; s < M::RL_MAXYS; ++s) p.ys[s] = sh->Y[yidx[s]];
-    lds_order();
+    SBM_LDS_FENCE();
     return p;
   }
   __device__ __forceinline__ Token eval(const Pending& p, double t) const {
@@ -1695,21 +1667,21 @@ struct PackedRowLaneSystem {
     for (int s = 0; s < M::RL_MAXJP; ++s) jp[s] = 0.0;
     M::class_dispatch(cls, t, p.ys, ps, k.f, jy, jp);
     k.f = cls >= 0 ? k.f : 0.0;
-    lds_order();
+    SBM_LDS_FENCE();
 #pragma unroll
     for (int s = 0; s < M::RL_MAXJP; ++s) sh->A[apos[s]] = jp[s];
 #pragma unroll
     for (int s = 0; s < M::RL_MAXJY; ++s) sh->JYL[jypos[s]] = jy[s];
-    lds_order();
+    SBM_LDS_FENCE();
     return k;
   }
   __device__ __forceinline__ void finish(const Token&, double, const double (&z)[1][NVX], double (&dz)[1][NVX]) const {
     double zc[NV], dc[NV], acol[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) { zc[i] = z[0][i]; acol[i] = acolp[i * SEG]; }
-    lds_order();
+    SBM_LDS_FENCE();
     M::apply_lds(jyl, acol, zc, dc);
-    lds_order();
+    SBM_LDS_FENCE();
 #pragma unroll
     for (int i = 0; i < NV; ++i) dz[0][i] = dc[i];
   }
@@ -1768,9 +1740,7 @@ __global__ void __launch_bounds__(64) sbm_sens_packed_kernel(sbm_kernel_args a) 
   sys.acolp = sh.A + seg * NV * SEG + li;
   __syncthreads();
 
-  const int goff = a.grid_off ? a.grid_off[traj] : 0;
-  const int glen = a.grid_len ? a.grid_len[traj] : a.n_t;
-  const double* tg = a.t_out + goff;
+  const auto [tg, glen] = sbm_grid_window(a, traj);
 
   double z[1][NVX];
 #pragma unroll
@@ -1787,11 +1757,7 @@ __global__ void __launch_bounds__(64) sbm_sens_packed_kernel(sbm_kernel_args a) 
     }
   };
   SbmTrajOut r = sbm_integrate<METHOD>(sys, z, tg, glen, a.opts, store);
-  if (li == 0 && live) {
-    if (a.status) a.status[traj] = r.status;
-    if (a.n_steps) a.n_steps[traj] = r.n_acc;
-    if (a.n_reject) a.n_reject[traj] = r.n_rej;
-  }
+  if (li == 0 && live) sbm_report(a, traj, r.status, r.n_acc, r.n_rej, false);
 }
 
 // v[lane] of a per-lane array held in registers: a binary select tree over the bits of `lane`.  The
@@ -1849,7 +1815,7 @@ __global__ void __launch_bounds__(64) sbm_imid_kernel(sbm_kernel_args a) {
   constexpr int RPL = Stepper::RPL;
   __shared__ SbmImidShared<M> sh;
   if ((int)blockIdx.x >= a.n_traj) return;
-  const int traj = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
+  const int traj = sbm_traj_of(a, blockIdx.x);
   const int lane = threadIdx.x;
   const int chunk = NCH > 1 ? (int)blockIdx.y : 0;
   const int col = lane + 64 * chunk;       // this lane's column of S
@@ -1858,9 +1824,7 @@ __global__ void __launch_bounds__(64) sbm_imid_kernel(sbm_kernel_args a) {
   st.setup(&sh, lane, chunk, a.P + (size_t)traj * M::NP);
   __syncthreads();
 
-  const int goff = a.grid_off ? a.grid_off[traj] : 0;
-  const int glen = a.grid_len ? a.grid_len[traj] : a.n_t;
-  const double* tg = a.t_out + goff;
+  const auto [tg, glen] = sbm_grid_window(a, traj);
   const bool with_sens = a.S != nullptr;   // wave-uniform
   const bool graded = a.opts.method == SBM_IMPLICIT_MIDPOINT_GRADED;
 
@@ -1983,338 +1947,5 @@ struct SbmImplicitFits {
   static constexpr bool adaptive = M::NV <= SBM_IMPLICIT_MAX_NV && sizeof(SbmImadShared<M>) <= 160u * 1024u;
 };
 
-// ---------------------------------------------------------------------------
-// host-side launcher used by sbm_plugin_main.hip
-// ---------------------------------------------------------------------------
-template <class T>
-struct SbmTypeTag { using type = T; };
-
-// ---- scratch of the persistent kernels: one buffer per (device, stream), grown on demand, never shrunk.  Launches on
-// one stream run one after the other, so they can share it; two contexts on two streams get one each. ----
-#include <map>
-#include <mutex>
-#include <utility>
-#include <stdlib.h>
-#include <stdio.h>
-struct SbmScratch {
-  void* p = nullptr;
-  size_t bytes = 0;
-  int* counter = nullptr;      // the work counter of a persistent launch (zeroed on the stream before every launch)
-};
-static hipError_t sbm_scratch_for(hipStream_t stream, size_t need, SbmScratch** out) {
-  static std::mutex mu;
-  static std::map<std::pair<int, void*>, SbmScratch> table;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  std::lock_guard<std::mutex> lock(mu);
-  SbmScratch& s = table[std::make_pair(dev, (void*)stream)];
-  if (!s.counter) {
-    e = hipMalloc((void**)&s.counter, 256);
-    if (e != hipSuccess) { s.counter = nullptr; return e; }
-  }
-  if (s.bytes < need) {
-    // work enqueued earlier on this stream may still read the old buffer
-    e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return e;
-    if (s.p) (void)hipFree(s.p);
-    s.p = nullptr;
-    s.bytes = 0;
-    e = hipMalloc(&s.p, need);
-    if (e != hipSuccess) { s.p = nullptr; return e; }
-    // zeroed once, on the stream: a first launch sees the same bytes whatever the allocator hands out
-    e = hipMemsetAsync(s.p, 0, need, stream);
-    if (e != hipSuccess) { (void)hipFree(s.p); s.p = nullptr; return e; }
-    s.bytes = need;
-  }
-  *out = &s;
-  return hipSuccess;
-}
-// how many workgroups of `kernel` the device holds at once (cached per kernel and device)
-static hipError_t sbm_resident_blocks(const void* kernel, int block, int* out) {
-  static std::mutex mu;
-  static std::map<std::pair<int, const void*>, int> cache;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = cache.find(std::make_pair(dev, kernel));
-  if (it == cache.end()) {
-    int per_cu = 0, cus = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0);
-    if (e != hipSuccess) return e;
-    e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return e;
-    if (per_cu < 1) per_cu = 1;
-    it = cache.emplace(std::make_pair(dev, kernel), per_cu * cus).first;
-  }
-  *out = it->second;
-  return hipSuccess;
-}
-// developer A/B switch: SBM_IEX_SEQ=0 runs chain models through sbm_iex_kernel as round 3 did
-static bool sbm_iex_seq_enabled() {
-  static const bool on = [] { const char* v = getenv("SBM_IEX_SEQ"); return !(v && v[0] == '0'); }();
-  return on;
-}
-
-template <class M>
-static int sbm_launch_model(int kind, const sbm_kernel_args* args, hipStream_t stream) {
-  const sbm_kernel_args a = *args;
-  if (a.n_traj <= 0) return (int)hipSuccess;
-  if (a.opts.method == SBM_IMPLICIT_EXTRAP) {
-    if constexpr (SbmIexFits<M>::value) {
-      const int nch = a.S ? (M::NK + 63) / 64 : 1;
-      if (nch > 1) {     // chunks combine status / counts with atomicMax
-        hipError_t e = hipSuccess;
-        if (a.status) e = hipMemsetAsync(a.status, 0, sizeof(int32_t) * (size_t)a.n_traj, stream);
-        if (e == hipSuccess && a.n_steps) e = hipMemsetAsync(a.n_steps, 0, sizeof(int32_t) * (size_t)a.n_traj, stream);
-        if (e == hipSuccess && a.n_reject) e = hipMemsetAsync(a.n_reject, 0, sizeof(int32_t) * (size_t)a.n_traj, stream);
-        if (e != hipSuccess) return (int)e;
-      }
-      if constexpr (SbmIexSeqFits<M>::value) {
-        // chain models, order <= 8: sequences side by side + persistent wavefronts (sbm_implicit_extrap_seq.hpp)
-        int K = a.opts.step_mult;
-        const double rtol = a.opts.rtol > 0.0 ? a.opts.rtol : 1e-8;
-        if (K <= 0) K = rtol >= 1e-4 ? 4 : (rtol >= 1e-6 ? 6 : 8);
-        if (K <= SbmIexSeqPlan<M>::KMAX && sbm_iex_seq_enabled()) {
-          const int n_work = a.n_traj * nch;
-          int resident = 0;
-          // columns held rotated (chain + one J_p entry per column: no select in the column step) unless the caller hands
-          // in initial sensitivities, which need not respect the structure
-          constexpr bool kRot = SbmIexSeqPlan<M>::ROT_OK;
-          const bool rot = kRot && a.s0 == nullptr;
-          const void* kfn = rot ? (const void*)sbm_iex_seq_kernel<M, kRot> : (const void*)sbm_iex_seq_kernel<M, false>;
-          hipError_t e = sbm_resident_blocks(kfn, 64, &resident);
-          if (e != hipSuccess) return (int)e;
-          const int grid = n_work < resident ? n_work : resident;
-          if (getenv("SBM_DEBUG_LAUNCH")) fprintf(stderr, "sbm_iex_seq_kernel: %d pieces of work, %d resident workgroups, grid %d\n", n_work, resident, grid);
-          SbmScratch* sc = nullptr;
-          e = sbm_scratch_for(stream, (size_t)grid * SbmIexSeqPlan<M>::BLOCK_DOUBLES * sizeof(double), &sc);
-          if (e != hipSuccess) return (int)e;
-          e = hipMemsetAsync(sc->counter, 0, sizeof(int), stream);
-          if (e != hipSuccess) return (int)e;
-          if (rot) hipLaunchKernelGGL((sbm_iex_seq_kernel<M, kRot>), dim3(grid), dim3(64), 0, stream, a, (double*)sc->p, sc->counter, n_work, nch);
-          else hipLaunchKernelGGL((sbm_iex_seq_kernel<M, false>), dim3(grid), dim3(64), 0, stream, a, (double*)sc->p, sc->counter, n_work, nch);
-          return (int)hipGetLastError();
-        }
-      }
-      hipLaunchKernelGGL((sbm_iex_kernel<M>), dim3(a.n_traj, nch), dim3(64), 0, stream, a);
-      return (int)hipGetLastError();
-    } else {
-      return (int)hipErrorInvalidConfiguration;
-    }
-  }
-  if (a.opts.method == SBM_IMPLICIT_ADAPTIVE) {
-    if constexpr (SbmImplicitFits<M>::adaptive) {
-      const int nch = a.S ? (M::NK + 63) / 64 : 1;
-      if (nch > 1) {     // chunks combine status / counts with atomicMax
-        hipError_t e = hipSuccess;
-        if (a.status) e = hipMemsetAsync(a.status, 0, sizeof(int32_t) * (size_t)a.n_traj, stream);
-        if (e == hipSuccess && a.n_steps) e = hipMemsetAsync(a.n_steps, 0, sizeof(int32_t) * (size_t)a.n_traj, stream);
-        if (e == hipSuccess && a.n_reject) e = hipMemsetAsync(a.n_reject, 0, sizeof(int32_t) * (size_t)a.n_traj, stream);
-        if (e != hipSuccess) return (int)e;
-      }
-      hipLaunchKernelGGL((sbm_imid_adaptive_kernel<M>), dim3(a.n_traj, nch), dim3(64), 0, stream, a);
-      return (int)hipGetLastError();
-    } else {
-      return (int)hipErrorInvalidConfiguration;
-    }
-  }
-  if (a.opts.method == SBM_IMPLICIT_MIDPOINT || a.opts.method == SBM_IMPLICIT_MIDPOINT_GRADED) {
-    // one trajectory per wave for both kinds (state only: S == NULL skips the column work)
-    if constexpr (SbmImplicitFits<M>::fixed) {
-      // state only: one wavefront; with sensitivities: one per chunk of 64 columns
-      const int nch = a.S ? (M::NK + 63) / 64 : 1;
-      hipLaunchKernelGGL((sbm_imid_kernel<M>), dim3(a.n_traj, nch), dim3(64), 0, stream, a);
-      return (int)hipGetLastError();
-    } else {
-      return (int)hipErrorInvalidConfiguration;   // see SbmImplicitFits
-    }
-  }
-  // J_y S on the matrix cores (sbm_sens_mfma.hpp) costs the same whatever the sparsity of J_y; the scalar kernels cost
-  // 2 FMAs per non-zero and column.  Measured on 20-state networks, 4096 vectors, DOPRI45 (bench.py "dense",
-  // profiles/r03, scalar / MFMA ms): 40 non-zeros (cascade20, twice the steps) 5.3 / 21.7; 60: 4.0 / 11.1; 120: 9.3 / 11.5;
-  // 220: 25.7 / 12.1; 400 (dense): 67.1 / 13.4 -- the matrix cores win from about 35 % density (round 2, one wavefront per
-  // SIMD: 45 %).  AUTO takes them from there (a static property of the model: a given model always runs the same
-  // kernel); SBM_VARIANT_MFMA forces them.
-  constexpr bool kMfmaPays = M::NV >= 16 && M::NV <= 64 && (long long)M::NNZ_JY * 100 >= 35LL * M::NV * M::NV;
-  // (DOP853 keeps twelve stage vectors alive -- on the matrix-core kernel they leave the register file: built, so that a
-  // forced variant answers, but AUTO keeps DOP853 on the row kernels)
-  if (kind == SBM_KIND_SENS && (a.opts.variant == SBM_VARIANT_MFMA ||
-                                (kMfmaPays && a.opts.method != SBM_DOP853 &&
-                                 (a.opts.variant == SBM_VARIANT_AUTO || a.opts.variant == SBM_VARIANT_SMALL_BATCH)))) {
-    // models beyond one state row per lane fall through to the scalar kernels
-    if constexpr (M::NV <= 64) {
-      constexpr int nch = SbmMfmaPlan<M>::NCH;
-      if (nch > 1) {
-        hipError_t e = hipSuccess;
-        if (a.status) e = hipMemsetAsync(a.status, 0, sizeof(int32_t) * (size_t)a.n_traj, stream);
-        if (e == hipSuccess && a.n_steps) e = hipMemsetAsync(a.n_steps, 0, sizeof(int32_t) * (size_t)a.n_traj, stream);
-        if (e == hipSuccess && a.n_reject) e = hipMemsetAsync(a.n_reject, 0, sizeof(int32_t) * (size_t)a.n_traj, stream);
-        if (e != hipSuccess) return (int)e;
-      }
-      dim3 grid(a.n_traj, nch), block(64);
-      if (a.opts.method == SBM_DOPRI45) hipLaunchKernelGGL((sbm_sens_mfma_kernel<M, SBM_DOPRI45>), grid, block, 0, stream, a);
-      else if (a.opts.method == SBM_DOP853) hipLaunchKernelGGL((sbm_sens_mfma_kernel<M, SBM_DOP853>), grid, block, 0, stream, a);
-      else hipLaunchKernelGGL((sbm_sens_mfma_kernel<M, SBM_RK4_FIXED>), grid, block, 0, stream, a);
-      return (int)hipGetLastError();
-    }
-  }
-  // small models: several trajectories per wavefront (sbm_sens_packed_kernel)
-  if constexpr (M::NV <= 32 && M::NK <= 32 && M::NV * (M::NK + 1) <= 256) {
-    constexpr int need = M::NV > M::NK ? M::NV : M::NK;
-    constexpr int SEG = need <= 4 ? 4 : (need <= 8 ? 8 : (need <= 16 ? 16 : 32));
-    // AUTO: small models ALWAYS run packed (round 2 switched at 2048 trajectories: a vector's result then depended on
-    // the size of the batch it travelled in -- the shard a rank owns, the subset a lazy-Jacobian fit re-integrates).  One
-    // trajectory alone in its wavefront costs what it costs in the unpacked kernels; the single-vector methods of the
-    // Python classes ask for SMALL_BATCH and keep the row kernels' lower latency.
-    if (kind == SBM_KIND_SENS && (a.opts.variant == SBM_VARIANT_PACKED || a.opts.variant == SBM_VARIANT_AUTO)) {
-      dim3 grid((a.n_traj + 64 / SEG - 1) / (64 / SEG)), block(64);
-      if (a.opts.method == SBM_DOPRI45) hipLaunchKernelGGL((sbm_sens_packed_kernel<M, SBM_DOPRI45, SEG>), grid, block, 0, stream, a);
-      else if (a.opts.method == SBM_DOP853) hipLaunchKernelGGL((sbm_sens_packed_kernel<M, SBM_DOP853, SEG>), grid, block, 0, stream, a);
-      else hipLaunchKernelGGL((sbm_sens_packed_kernel<M, SBM_RK4_FIXED, SEG>), grid, block, 0, stream, a);
-      return (int)hipGetLastError();
-    }
-  }
-  if (kind == SBM_KIND_SENS) {
-    // row-lane / row-group kernels whenever the model fits one row + one column per lane.  Even when
-    // every row is a class of its own they evaluate NCLASS <= NV row bodies per stage where the per-wave
-    // kernel evaluates all NV rows on every lane (measured on random networks with 6 and 9 classes of 11
-    // and 17 rows: 1.6x faster than per-wave)
-    constexpr bool kRowLaneOk = (M::NV <= 64 && M::NK <= 64);
-    constexpr bool kRowLanePays = kRowLaneOk;
-    constexpr bool kRowGroupOk = M::RG0::RG_OK;   // any number of columns (chunks of them), up to four rows per lane
-    // The per-wave kernel keeps all NV rows of ceil((NK+1)/64) columns on every lane: for a large model that is
-    // minutes of compile time for a kernel whose stage vectors live in scratch.  Where the row-group form exists
-    // it is not instantiated beyond 4096 sensitivity entries, and opts.variant becomes a no-op for that model.
-    constexpr bool kPerWaveBuilt = !(kRowGroupOk && M::NV * (M::NK + 1) > 4096);
-    const bool rowlane = a.opts.variant == SBM_VARIANT_ROW_LANE ||
-                         ((a.opts.variant == SBM_VARIANT_AUTO || a.opts.variant == SBM_VARIANT_SMALL_BATCH ||
-                           a.opts.variant == SBM_VARIANT_MFMA || a.opts.variant == SBM_VARIANT_PACKED) && kRowLanePays);
-    // row-group kernel: the row-lane kernel with the rows of a column split over several lanes,
-    // when the emitter found a split that cuts the elements per lane (M::RG_OK)
-    if constexpr (kRowGroupOk) {
-      if (a.opts.variant == SBM_VARIANT_ROW_GROUP || a.opts.variant == SBM_VARIANT_AUTO ||
-          a.opts.variant == SBM_VARIANT_SMALL_BATCH || a.opts.variant == SBM_VARIANT_MFMA ||
-          a.opts.variant == SBM_VARIANT_PACKED || !kPerWaveBuilt) {
-        // Two splits of the same form (emit_rowgroup.py): RG0 for throughput; RG1 -- more, smaller column chunks,
-        // fewer elements per lane -- while all its wavefronts are resident at once (2048: two per SIMD; a wavefront of
-        // this split issues ~40 % of the other's instructions per step, so two of them sharing a SIMD still finish a step
-        // sooner than one of the other alone): a single parameter vector, a serial optimiser's call, is latency-bound.
-        // Opt-in (SBM_VARIANT_SMALL_BATCH: what the single-vector methods of the Python classes ask for): the two
-        // splits take different step sequences, and a batch call's rows must not depend on how many rows it has.
-        const bool small_batch = !std::is_same<typename M::RG1, typename M::RG0>::value &&
-                                 a.opts.variant == SBM_VARIANT_SMALL_BATCH && (long long)a.n_traj * M::RG1::RG_NCH <= 2048;
-        auto go = [&](auto layout_tag) -> int {
-          using L = typename decltype(layout_tag)::type;
-          dim3 grid(a.n_traj, L::RG_NCH), block(64);
-          if constexpr (L::RG_NCH > 1) {
-            hipError_t e = hipSuccess;
-            if (a.status) e = hipMemsetAsync(a.status, 0, sizeof(int32_t) * (size_t)a.n_traj, stream);
-            if (e == hipSuccess && a.n_steps) e = hipMemsetAsync(a.n_steps, 0, sizeof(int32_t) * (size_t)a.n_traj, stream);
-            if (e == hipSuccess && a.n_reject) e = hipMemsetAsync(a.n_reject, 0, sizeof(int32_t) * (size_t)a.n_traj, stream);
-            if (e != hipSuccess) return (int)e;
-          }
-          if (a.opts.method == SBM_DOPRI45)
-            hipLaunchKernelGGL((sbm_sens_rowgroup_kernel<M, L, SBM_DOPRI45>), grid, block, 0, stream, a);
-          else if (a.opts.method == SBM_DOP853) {
-            // (instantiated for its own split and the small-batch one only)
-            if constexpr (std::is_same<L, typename M::RG2>::value || std::is_same<L, typename M::RG1>::value)
-              hipLaunchKernelGGL((sbm_sens_rowgroup_kernel<M, L, SBM_DOP853>), grid, block, 0, stream, a);
-            else
-              return (int)hipErrorInvalidConfiguration;
-          } else
-            hipLaunchKernelGGL((sbm_sens_rowgroup_kernel<M, L, SBM_RK4_FIXED>), grid, block, 0, stream, a);
-          return (int)hipGetLastError();
-        };
-        // DOP853 keeps twelve stage vectors alive: its own split, planned for smaller shares per lane (RG2)
-        if (a.opts.method == SBM_DOP853 && !small_batch) return go(SbmTypeTag<typename M::RG2>{});
-        return small_batch ? go(SbmTypeTag<typename M::RG1>{}) : go(SbmTypeTag<typename M::RG0>{});
-      }
-    }
-    if (a.opts.method == SBM_DOP853) {
-      // beside the row-group form: the row-lane kernel (twelve stage vectors of NV rows per lane: beyond ~16 state
-      // variables they leave the register file and the kernel runs out of scratch -- correct, slow), then the per-wave one
-      if constexpr (kRowLaneOk && M::NV <= 32) {
-        if (a.opts.variant != SBM_VARIANT_PER_WAVE) {
-          hipLaunchKernelGGL((sbm_sens_rowlane_kernel<M, SBM_DOP853>), dim3(a.n_traj), dim3(64), 0, stream, a);
-          return (int)hipGetLastError();
-        }
-      }
-      if constexpr (kPerWaveBuilt && M::NV * ((M::NK + 64) / 64) <= 64) {
-        hipLaunchKernelGGL((sbm_sens_kernel<M, SBM_DOP853>), dim3(a.n_traj), dim3(64), 0, stream, a);
-        return (int)hipGetLastError();
-      } else {
-        return (int)hipErrorInvalidConfiguration;
-      }
-    }
-    if constexpr (kRowLaneOk) {
-      if (rowlane) {
-        dim3 grid(a.n_traj), block(64);
-        if (a.opts.method == SBM_DOPRI45)
-          hipLaunchKernelGGL((sbm_sens_rowlane_kernel<M, SBM_DOPRI45>), grid, block, 0, stream, a);
-        else
-          hipLaunchKernelGGL((sbm_sens_rowlane_kernel<M, SBM_RK4_FIXED>), grid, block, 0, stream, a);
-        return (int)hipGetLastError();
-      }
-    }
-    if constexpr (kPerWaveBuilt) {
-      dim3 grid(a.n_traj), block(64);
-      if (a.opts.method == SBM_DOPRI45) hipLaunchKernelGGL((sbm_sens_kernel<M, SBM_DOPRI45>), grid, block, 0, stream, a);
-      else hipLaunchKernelGGL((sbm_sens_kernel<M, SBM_RK4_FIXED>), grid, block, 0, stream, a);
-    }
-  } else {
-    // one trajectory per wave until the chip is full of lane-per-trajectory waves anyway
-    constexpr bool kRowsOk = (M::NV <= 256);   // up to four state rows per lane
-    // one trajectory per LANE keeps NV stage-vector rows per lane: beyond 64 rows only the rows kernel is built
-    constexpr bool kLaneBuilt = !(kRowsOk && M::NV > 64);
-    // Which state-only kernel (measured on cascade20, DOPRI45, scripts/dev_state_big.py): one trajectory per
-    // wavefront up to 2047 trajectories (0.2 ms per 1024, lowest latency); several per wavefront from there
-    // (0.14 ms per 1024: 0.56 ms at 4096, 3.3 ms at 32768); one trajectory per LANE costs 2.6 - 2.9 ms whatever
-    // the batch up to 65536 (one serial chain per lane, 64 of them per wavefront) and wins from ~20000 on --
-    // for small models only: beyond 32 state variables its stage vectors leave the register file.
-    constexpr int kLaneFrom = (M::NV <= 32) ? 20480 : 65536;
-    // several trajectories per wavefront once the chip is full: models of up to 32 state variables
-    if constexpr (M::NV <= 32 && M::NV >= 2) {
-      if (a.n_traj >= 2048 && a.n_traj < kLaneFrom && a.opts.variant == SBM_VARIANT_AUTO) {
-        // DOPRI45 reduces its error norm inside a segment: widths 16 / 32 (DPP).  Segment sums through LDS for
-        // other widths were tried (20 lanes: three trajectories per wavefront): 0.53 against 0.49 ms -- the LDS
-        // round trip per step and a third trajectory to wait for cost more than the denser packing gains.
-        // RK4 reduces nothing: the width is the state variables rounded up to a multiple of four lanes.
-        constexpr int SEG_A = M::NV <= 16 ? 16 : 32;
-        constexpr int SEG_F = (M::NV + 3) / 4 * 4;
-        if (a.opts.method == SBM_DOPRI45) {
-          dim3 grid((a.n_traj + 64 / SEG_A - 1) / (64 / SEG_A)), block(64);
-          hipLaunchKernelGGL((sbm_state_packed_kernel<M, SBM_DOPRI45, SEG_A>), grid, block, 0, stream, a);
-        } else if (a.opts.method == SBM_DOP853) {
-          dim3 grid((a.n_traj + 64 / SEG_A - 1) / (64 / SEG_A)), block(64);
-          hipLaunchKernelGGL((sbm_state_packed_kernel<M, SBM_DOP853, SEG_A>), grid, block, 0, stream, a);
-        } else {
-          dim3 grid((a.n_traj + 64 / SEG_F - 1) / (64 / SEG_F)), block(64);
-          hipLaunchKernelGGL((sbm_state_packed_kernel<M, SBM_RK4_FIXED, SEG_F>), grid, block, 0, stream, a);
-        }
-        return (int)hipGetLastError();
-      }
-    }
-    if constexpr (kRowsOk) {
-      if (((a.n_traj < kLaneFrom || a.opts.variant == SBM_VARIANT_ROW_LANE || a.opts.variant == SBM_VARIANT_ROW_GROUP) &&
-           a.opts.variant != SBM_VARIANT_PER_WAVE) || !kLaneBuilt || a.opts.method == SBM_DOP853) {
-        dim3 grid(a.n_traj), block(64);
-        if (a.opts.method == SBM_DOPRI45)
-          hipLaunchKernelGGL((sbm_state_rows_kernel<M, SBM_DOPRI45>), grid, block, 0, stream, a);
-        else if (a.opts.method == SBM_DOP853)
-          hipLaunchKernelGGL((sbm_state_rows_kernel<M, SBM_DOP853>), grid, block, 0, stream, a);
-        else
-          hipLaunchKernelGGL((sbm_state_rows_kernel<M, SBM_RK4_FIXED>), grid, block, 0, stream, a);
-        return (int)hipGetLastError();
-      }
-    }
-    if (a.opts.method == SBM_DOP853) return (int)hipErrorInvalidConfiguration;   // (more than 256 state variables)
-    if constexpr (kLaneBuilt) {
-      dim3 grid((a.n_traj + 63) / 64), block(64);
-      if (a.opts.method == SBM_DOPRI45) hipLaunchKernelGGL((sbm_state_kernel<M, SBM_DOPRI45>), grid, block, 0, stream, a);
-      else hipLaunchKernelGGL((sbm_state_kernel<M, SBM_RK4_FIXED>), grid, block, 0, stream, a);
-    }
-  }
-  return (int)hipGetLastError();
-}
+// the host side: which of these kernels a call runs (sbm_launch_model, used by sbm_plugin_main.hip)
+#include "sbm_launch.hpp"

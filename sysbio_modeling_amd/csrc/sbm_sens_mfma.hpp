@@ -60,17 +60,16 @@ struct MfmaSystem {
   int yidx[M::RL_MAXYS], jdpos[M::RL_MAXJY], apos[M::RL_MAXJP];
   double ps[M::RL_MAXPS];
 
-  __device__ __forceinline__ static void lds_order() { __atomic_signal_fence(__ATOMIC_SEQ_CST); }
   struct Pending { double ys[M::RL_MAXYS]; };
   struct Token { double f; };
 
   __device__ __forceinline__ Pending issue(double, const double (&z)[1][NVX]) const {
     Pending p;
     sh->Y[lane] = z[0][NV];
-    lds_order();
+    SBM_LDS_FENCE();
 #pragma unroll
     for (int s = 0; s < M::RL_MAXYS; ++s) p.ys[s] = sh->Y[yidx[s]];
-    lds_order();
+    SBM_LDS_FENCE();
     return p;
   }
   __device__ __forceinline__ Token eval(const Pending& p, double t) const {
@@ -83,12 +82,12 @@ struct MfmaSystem {
     for (int s = 0; s < M::RL_MAXJP; ++s) jp[s] = 0.0;
     M::class_dispatch(cls, t, p.ys, ps, k.f, jy, jp);
     k.f = cls >= 0 ? k.f : 0.0;
-    lds_order();
+    SBM_LDS_FENCE();
 #pragma unroll
     for (int s = 0; s < M::RL_MAXJY; ++s) sh->JD[jdpos[s]] = jy[s];
 #pragma unroll
     for (int s = 0; s < M::RL_MAXJP; ++s) sh->A[apos[s]] = jp[s];
-    lds_order();
+    SBM_LDS_FENCE();
     return k;
   }
   __device__ __forceinline__ void extra_out(const Token& k, double (&dz)[1][NVX]) const { dz[0][NV] = k.f; }
@@ -118,7 +117,7 @@ struct MfmaSystem {
         for (int r = 0; r < 4; ++r) dz[0][(rt * CT + ct) * 4 + r] = acc[r];
       }
     }
-    lds_order();
+    SBM_LDS_FENCE();
   }
   __device__ __forceinline__ void rhs(double t, const double (&z)[1][NVX], double (&dz)[1][NVX]) const {
     const Token k = eval(issue(t, z), t);
@@ -174,7 +173,7 @@ __global__ void __launch_bounds__(64, SbmMfmaPlan<M>::MIN_WAVES) sbm_sens_mfma_k
   static_assert(MNV <= 64, "MFMA sensitivity kernel: one state row per lane");
   __shared__ Sh sh;
   if ((int)blockIdx.x >= a.n_traj) return;
-  const int traj = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
+  const int traj = sbm_traj_of(a, blockIdx.x);
   const int lane = threadIdx.x;
   const int chunk = NCH > 1 ? (int)blockIdx.y : 0;
   const int cbase = chunk * 16 * CT;
@@ -206,9 +205,7 @@ __global__ void __launch_bounds__(64, SbmMfmaPlan<M>::MIN_WAVES) sbm_sens_mfma_k
   }
   __syncthreads();
 
-  const int goff = a.grid_off ? a.grid_off[traj] : 0;
-  const int glen = a.grid_len ? a.grid_len[traj] : a.n_t;
-  const double* tg = a.t_out + goff;
+  const auto [tg, glen] = sbm_grid_window(a, traj);
   const int lr = lane & 15, lq = lane >> 4;
 
   // element (rt, ct, r) of this lane = S[16 rt + lq + 4 r][cbase + 16 ct + lr]
@@ -241,17 +238,6 @@ __global__ void __launch_bounds__(64, SbmMfmaPlan<M>::MIN_WAVES) sbm_sens_mfma_k
     }
   };
 
-  SbmTrajOut r = sbm_integrate<METHOD>(sys, z, tg, glen, a.opts, store);
-
-  if (lane == 0) {
-    if constexpr (NCH > 1) {
-      if (a.status) atomicMax(a.status + traj, r.status);
-      if (a.n_steps) atomicMax(a.n_steps + traj, r.n_acc);
-      if (a.n_reject) atomicMax(a.n_reject + traj, r.n_rej);
-    } else {
-      if (a.status) a.status[traj] = r.status;
-      if (a.n_steps) a.n_steps[traj] = r.n_acc;
-      if (a.n_reject) a.n_reject[traj] = r.n_rej;
-    }
-  }
+  const SbmTrajOut r = sbm_integrate<METHOD>(sys, z, tg, glen, a.opts, store);
+  if (lane == 0) sbm_report(a, traj, r.status, r.n_acc, r.n_rej, NCH > 1);
 }
