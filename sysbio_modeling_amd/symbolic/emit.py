@@ -207,14 +207,27 @@ class _ExprPrinter(C99CodePrinter):
         self._smap = symbol_map
         self._rcp = rcp
         self._lang = lang
+        # subtrees (of the normalised expression) printed as a NAME: values another statement already holds
+        # (emit_rowlane.py: operations shared by several classes).  Everything around them prints as it would without.
+        self.shared = {}
 
-    def doprint(self, expr, assign_to=None):
-        # x**(-n) -> RCP(x**n) BEFORE printing: the stock Mul printer would otherwise
-        # collect negative powers into an a/b division
-        expr = sympy.sympify(expr).replace(
+    @staticmethod
+    def normalised(expr):
+        """the tree doprint prints: x**(-n) -> RCP(x**n), because the stock Mul printer would otherwise collect
+        negative powers into an a/b division"""
+        return sympy.sympify(expr).replace(
             lambda e: e.is_Pow and e.exp.is_number and e.exp.is_negative,
             lambda e: _RCP(sympy.Pow(e.base, -e.exp)))
-        return super().doprint(expr, assign_to)
+
+    def doprint(self, expr, assign_to=None):
+        return super().doprint(self.normalised(expr), assign_to)
+
+    def _print(self, expr, **kwargs):
+        if self.shared and isinstance(expr, sympy.Basic):
+            name = self.shared.get(expr)
+            if name is not None:
+                return name
+        return super()._print(expr, **kwargs)
 
     def _print_Function(self, expr):
         if expr.func == _RCP:
@@ -449,7 +462,7 @@ def emit_c(spec: ModelSpec, derived: Derived = None) -> str:
 # ----------------------------------------------------------------------------
 # HIP device struct
 # ----------------------------------------------------------------------------
-def emit_hip(spec: ModelSpec, derived: Derived = None) -> str:
+def emit_hip(spec: ModelSpec, derived: Derived = None, class_hoist: bool = True) -> str:
     """Header defining ``struct SbmModel`` consumed by csrc/sbm_integrators.hpp.
 
     ``eval_f``   : state RHS only (state-only kernels, one trajectory per lane).
@@ -458,6 +471,8 @@ def emit_hip(spec: ModelSpec, derived: Derived = None) -> str:
     ``apply_col``: dz = J_y z + J_p[:, scol] for ONE column held in registers;
                    fully unrolled with static indices so that ``z``/``dz`` stay
                    in VGPRs.
+    ``class_hoist``: evaluate an expensive operation that several row-lane classes have in common once, on
+                   selected operands (emit_rowlane.py); False prints every class body in full, as a reference.
     """
     d = derived or Derived(spec)
     n, k = spec.n_vars, spec.n_sens
@@ -558,7 +573,8 @@ def emit_hip(spec: ModelSpec, derived: Derived = None) -> str:
 
     # ---- row-lane form: SIMD across isomorphic equations (emit_rowlane.py) ----
     L += emit_rowlane.emit_rowlane_members(spec, d, rl_meta,
-                                           lambda smap: _ExprPrinter(smap, rcp="SBM_RCP(%s)", lang='hip'))
+                                           lambda smap: _ExprPrinter(smap, rcp="SBM_RCP(%s)", lang='hip'),
+                                           hoist=class_hoist)
     L += [""] + emit_rowgroup.emit_members(spec, d, rg_layout, tag='RG0')
     L += emit_rowgroup.emit_members(spec, d, rg_layout1, tag='RG1', alias_of='RG0')
     L += emit_rowgroup.emit_members(spec, d, rg_layout2, tag='RG2', alias_of='RG0')

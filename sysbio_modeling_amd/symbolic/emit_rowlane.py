@@ -17,6 +17,7 @@ and prints
 """
 from __future__ import annotations
 
+import re
 from collections import OrderedDict
 
 import sympy
@@ -92,8 +93,167 @@ def emit_rowlane_tables(spec, d, printer_factory):
     return L, meta
 
 
-def emit_rowlane_members(spec, d, meta, make_printer):
-    """Member functions of ``struct SbmModel`` for the row-lane kernel."""
+# Operations worth sharing between classes, in VALU issue slots of a wavefront (fp64 on gfx950: v_rcp_f64 and the other
+# transcendentals issue at quarter rate; SBM_RCP adds two Newton steps of two FMAs).  A select is two v_cndmask_b32.
+_OP_COST = {'rcp': 8, 'sqrt': 16, 'exp': 40, 'log': 40, 'pow': 80, 'call': 40, 'add': 1, 'mul': 1}
+_SEL_COST = 2
+_LEAF = re.compile(r'(?<![A-Za-z0-9_])(?:ys\[\d+\]|ps\[\d+\]|c\d+_x\d+|h\d+|t)(?![A-Za-z0-9_])')
+_NAME = re.compile(r'(?<![A-Za-z0-9_])(?:c\d+_x\d+|h\d+)(?![A-Za-z0-9_])')
+
+
+def _op_kind(node):
+    """which entry of _OP_COST the root of ``node`` is (None: a leaf)"""
+    if node.is_Function:
+        return {'SBM_RCP': 'rcp', 'exp': 'exp', 'log': 'log'}.get(node.func.__name__, 'call')
+    if node.is_Pow:
+        if node.exp.is_Integer and 1 <= int(node.exp) <= 4:
+            return 'mul'
+        return 'sqrt' if node.exp == sympy.Rational(1, 2) else 'pow'
+    if node.is_Add:
+        return 'add'
+    if node.is_Mul:
+        return 'mul'
+    return None
+
+
+def _tree_cost(node):
+    kind = _op_kind(node)
+    if kind is None:
+        return 0
+    n = int(node.exp) - 1 if node.is_Pow and kind == 'mul' else max(len(node.args) - 1, 1)
+    return _OP_COST[kind] * n + sum(_tree_cost(a) for a in node.args)
+
+
+def _plan_hoist(per_class, pr):
+    """Operations that several classes have in common, to be evaluated ONCE on selected operands.
+
+    Every class body is evaluated on every lane (class_dispatch below), so an operation that occurs in k classes costs k
+    times what a lane needs.  Where the classes' subtrees under an expensive root (reciprocal, sqrt, exp, log, pow)
+    print to the SAME TEXT up to the operands at the leaves -- ys[.], ps[.], CSE temporaries, earlier shared values --
+    the text is emitted once with each differing leaf replaced by a select chain on the class:
+    op(sel(c, a, b)) and sel(c, op(a), op(b)) are the same value in every lane, and because the shared statement IS
+    each class's own text after substitution of its leaves, operand order, association and what the compiler may
+    contract into FMAs are those of the unshared form.  The class bodies are printed as before, with the subtree
+    replaced by the shared name (``_ExprPrinter.shared``).
+
+    Greedy, most expensive trees first; a group is taken when cost(tree) * (k - 1) exceeds the selects it adds,
+    _SEL_COST per differing leaf and extra class.  Classes without the operation simply do not take part.
+    Returns ([{node: name} per class], [dict(name, shape, leaves={class: [leaf texts]}, classes=[...])])."""
+    n_cls = len(per_class)
+    shared = [{} for _ in range(n_cls)]
+    hoisted = []
+    rejected = set()
+    exprs = [[pr.normalised(e) for _, e in repl] + [pr.normalised(e) for e in red] for repl, red in per_class]
+    temps = [[str(s) for s, _ in repl] for repl, _ in per_class]
+
+    def depends(name, on, seen):
+        """does statement ``name`` (a temporary or a shared value) use ``on``, directly or not"""
+        if name in seen:
+            return False
+        seen.add(name)
+        for ci in range(n_cls):
+            if name in temps[ci]:
+                pr.shared = shared[ci]
+                uses = _NAME.findall(pr.doprint(exprs[ci][temps[ci].index(name)]))
+                break
+        else:
+            h = next(h for h in hoisted if h['name'] == name)
+            uses = [x for lv in h['leaves'].values() for x in lv if _NAME.fullmatch(x)]
+        return any(u == on or depends(u, on, seen) for u in uses)
+
+    def printed(ci, node):
+        """text of ``node`` as class ci prints it, values shared so far by name; -> (shape, leaves)"""
+        # a temporary that is a PRODUCT enters the shared text as its definition, not by name: where it feeds a sum the
+        # compiler contracts the two into one FMA, which it could not do through a select of two finished products
+        pr.shared = {k: v for k, v in shared[ci].items() if k != node}
+        for (sym, _), e in zip(per_class[ci][0], exprs[ci]):
+            if _op_kind(e) == 'mul':
+                pr.shared[sym] = "(%s)" % pr._print(e)
+        text = pr._print(node)
+        return _LEAF.sub('@', text), _LEAF.findall(text)
+
+    def n_selects(leaves):
+        """selects the operands cost: per leaf position, one for every class that differs from the most common operand"""
+        return sum(len(pos) - max(pos.count(x) for x in pos) for pos in zip(*leaves))
+
+    def cyclic(h):
+        feeds = [x for lv in h['leaves'].values() for x in lv if _NAME.fullmatch(x)]
+        return any(depends(x, h['name'], set()) for x in feeds)
+
+    while True:
+        groups = OrderedDict()     # (shape, occurrence) -> {class: (node, leaves)}
+        for ci in range(n_cls):
+            seen, count = set(), {}
+            for e in exprs[ci]:
+                walk = sympy.preorder_traversal(e)
+                for node in walk:
+                    if node in shared[ci]:
+                        walk.skip()
+                        continue
+                    if node in seen or _op_kind(node) in (None, 'add', 'mul'):
+                        continue
+                    seen.add(node)
+                    shape, leaves = printed(ci, node)
+                    occ = count.get(shape, 0)
+                    count[shape] = occ + 1
+                    groups.setdefault((shape, occ), OrderedDict())[ci] = (node, leaves)
+        best = None
+        for key, members in groups.items():
+            if len(members) < 2 or key in rejected:
+                continue
+            cost = _tree_cost(next(iter(members.values()))[0])
+            gain = cost * (len(members) - 1) - _SEL_COST * n_selects([lv for _, lv in members.values()])
+            if gain > 0 and (best is None or cost > best[0]):
+                best = (cost, key, members)
+        if best is None:
+            break
+        _, key, members = best
+        name = 'h%d' % len(hoisted)
+        h = dict(name=name, shape=key[0], classes=list(members), nodes={ci: nd for ci, (nd, _) in members.items()},
+                 leaves={ci: lv for ci, (_, lv) in members.items()})
+        hoisted.append(h)
+        for ci, (node, _) in members.items():
+            shared[ci][node] = name
+        # a class's temporary that feeds the shared value must not itself need it (two classes with the same two
+        # operations nested in opposite orders): such a group is left alone
+        if cyclic(h):
+            hoisted.pop()
+            for ci, (node, _) in members.items():
+                del shared[ci][node]
+            rejected.add(key)
+    # the larger trees were planned first: print them again, so that a smaller operation inside them that was shared
+    # afterwards (it occurs elsewhere as well) is used by name there too
+    for h in hoisted:
+        again = {ci: printed(ci, h['nodes'][ci]) for ci in h['classes']}
+        if len({shape for shape, _ in again.values()}) == 1:
+            old = (h['shape'], h['leaves'])
+            h['shape'], h['leaves'] = next(iter(again.values()))[0], {ci: lv for ci, (_, lv) in again.items()}
+            if cyclic(h):
+                h['shape'], h['leaves'] = old
+    pr.shared = {}
+    return shared, hoisted
+
+
+def _sel_template(h):
+    """the shared statement's right-hand side: the common text, each leaf the classes disagree on as a select chain whose
+    default is the operand most of the participating classes have"""
+    cls = h['classes']
+    parts = h['shape'].split('@')
+    out = [parts[0]]
+    for pos in range(len(parts) - 1):
+        col = [h['leaves'][ci][pos] for ci in cls]
+        expr = max(col, key=lambda x: (col.count(x), len(col) - col[::-1].index(x)))
+        default = expr
+        for ci in reversed(cls):
+            if h['leaves'][ci][pos] != default:
+                expr = "SBM_SEL(is%d, %s, %s)" % (ci, h['leaves'][ci][pos], expr)
+        out += [expr, parts[pos + 1]]
+    return "".join(out)
+
+
+def emit_rowlane_members(spec, d, meta, make_printer, hoist=True):
+    """Member functions of ``struct SbmModel`` for the row-lane kernel.  ``hoist=False``: every class body in full
+    (the reference form the shared one is checked against, tests/test_class_hoist.py)."""
     n = spec.n_vars
     classes = meta['classes']
     L = ["  // ---- row-lane form (sbm_sens_rowlane_kernel) ----",
@@ -127,16 +287,46 @@ def emit_rowlane_members(spec, d, meta, make_printer):
     # because other lanes read these registers with v_readlane.  The LAST class is the default of
     # the select chain (n-1 selects per output instead of n): lanes without a row (cls = -1) end up
     # with its values, which the kernels discard (spare LDS slots) or zero (f).
-    bodies = []
-    for ci, c in enumerate(classes):
-        L.append("    // class %d: rows %s" % (ci, ", ".join(str(r) for r in c['rows'])))
-        repl, red = cse(list(c['canon']), symbols=sympy.numbered_symbols('c%d_x' % ci), optimizations='basic')
-        for sym, e in repl:
-            L.append("    const double %s = %s;" % (sym, pr.doprint(e)))
-        bodies.append([pr.doprint(e) for e in red])
     last = len(classes) - 1
     for ci in range(last):
         L.append("    const bool is%d = (cls == %d);" % (ci, ci))
+    is_last_at = len(L)   # (the last class is the default of the output chains; a shared operand may still select on it)
+    per_class = [cse(list(c['canon']), symbols=sympy.numbered_symbols('c%d_x' % ci), optimizations='basic')
+                 for ci, c in enumerate(classes)]
+    shared, hoisted = _plan_hoist(per_class, pr) if hoist and len(classes) > 1 else ([{} for _ in classes], [])
+    # statements by name: the classes' CSE temporaries in their own order, a shared operation right before its first
+    # use -- with the temporaries of OTHER classes that feed it pulled ahead of it
+    stmts = OrderedDict()
+    for ci, (repl, _) in enumerate(per_class):
+        pr.shared = shared[ci]
+        for sym, e in repl:
+            stmts[str(sym)] = "    const double %s = %s;" % (sym, pr.doprint(e))
+    for h in hoisted:
+        stmts[h['name']] = "    const double %s = %s;   // classes %s" % (
+            h['name'], _sel_template(h), ", ".join(str(ci) for ci in h['classes']))
+    emitted = set()
+
+    def emit_stmt(name):
+        if name in emitted:
+            return
+        emitted.add(name)
+        for dep in _NAME.findall(stmts[name].split('=', 1)[1]):
+            if dep in stmts:
+                emit_stmt(dep)
+        L.append(stmts[name])
+
+    bodies = []
+    for ci, c in enumerate(classes):
+        L.append("    // class %d: rows %s" % (ci, ", ".join(str(r) for r in c['rows'])))
+        pr.shared = shared[ci]
+        for sym, _ in per_class[ci][0]:
+            emit_stmt(str(sym))
+        bodies.append([pr.doprint(e) for e in per_class[ci][1]])
+    pr.shared = {}
+    for h in hoisted:   # (those the outputs use directly)
+        emit_stmt(h['name'])
+    if any("(is%d," % last in ln for ln in L[is_last_at:]):
+        L.insert(is_last_at, "    const bool is%d = (cls == %d);" % (last, last))
 
     def chain(kind, k):
         """value of output (kind, k): the last class's expression (or 0), overridden class by class"""
