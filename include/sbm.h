@@ -444,11 +444,16 @@ int sbm_lm_trust_step_ex(sbm_ctx* ctx, const double* J_dev, const double* r_dev,
  * in one launch: actual and predicted relative reduction, their ratio, the radius / lambda update (ratio <= 1/4: shrink
  * by 1/2 or by the parabola-fit factor down to 1/10; ratio >= 3/4 or lambda = 0: Delta = 2 ||D delta||), acceptance
  * (ratio >= 1e-4 and an integrable trial point) and the convergence tests (info 1: both reductions <= ftol with
- * ratio <= 2; info 2: Delta <= xtol ||D theta||).
+ * ratio <= 2; info 2: Delta <= xtol ||D theta||).  With |r|^2 = 2 cost lmder's quantities are prered = pred / cost,
+ * dirder = gtx / (2 cost), actred = 1 - cost_trial / cost (-1 where 0.1 |r_trial| >= |r| or the trial point is unusable).
+ * Where this departs from lmder.f, on purpose: a step status != 0 halves Delta, keeps lambda and the point and tests no
+ * convergence; cost = 0 is divided by 1; pred <= 0 (possible for a clipped step only; lmder's prered is a sum of squares)
+ * gives ratio 0 like lmder's prered = 0, so that no uphill step is taken; and ||D theta|| of info 2 is that of the
+ * current point, before sbm_lm_accept moves it (lmder measures the point the iteration ends on).
  *   cost [V]            0.5 |r|^2 at the current points       norms_trial, status_trial [V]   |r|^2 and integration
  *   pred, dxnorm, gtx, step_status [V]   from sbm_lm_trust_step_ex     status of the trial points (sbm_*_batch)
  *   theta, dscale [V][q]                 current points, scaling
- *   iteration, first                     iteration index (recorded in n_iter on convergence); first != 0: lmder's
+ *   iteration, first                     iteration index from 0 (n_iter = iteration + 1 on convergence); first != 0: lmder's
  *                                        first-iteration rule Delta = min(Delta, ||D delta||)
  *   radius, lambda, done, n_iter [V]     in / out            accept [V]  out: 1 = the trial point is taken
  *   counters [2]                         out: starts still running, trial points accepted

@@ -1816,7 +1816,8 @@ __global__ void __launch_bounds__(256) k_lm_update(LmUpdateArgs a) {
   }
   const bool ok = ratio >= 1.0e-4 && cost_t < 1.0e300;
   a.accept[v] = ok ? 1 : 0;
-  // lmder's convergence tests (info 1, 2); ||D theta|| at the point the iteration ends on
+  // lmder's convergence tests (info 1, 2); ||D theta|| at the point the iteration started from (the current point, before
+  // sbm_lm_accept moves it: lmder itself measures the point it ends on)
   double xn2 = 0.0;
   for (int c = 0; c < a.q; ++c) {
     const double t = a.dscale[(size_t)v * a.q + c] * a.theta[(size_t)v * a.q + c];
@@ -1864,7 +1865,9 @@ __global__ void __launch_bounds__(256) k_lm_accept(const int32_t* __restrict__ a
   const size_t nJ = (size_t)M * q;
   const double2* src = reinterpret_cast<const double2*>(J_t + (size_t)v * nJ);
   double2* dst = reinterpret_cast<double2*>(J + (size_t)v * nJ);
-  if ((nJ & 1) == 0 && ((((size_t)v * nJ) & 1) == 0)) {
+  // 16-byte accesses only where both rows really are 16-byte aligned: an even row length and element offset say nothing
+  // about the base pointers (a view that starts one double into an allocation is 8-byte aligned)
+  if ((nJ & 1) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
     for (size_t e = threadIdx.x + (size_t)blockIdx.y * blockDim.x; e < nJ / 2; e += (size_t)blockDim.x * gridDim.y) dst[e] = src[e];
   } else {
     for (size_t e = threadIdx.x + (size_t)blockIdx.y * blockDim.x; e < nJ; e += (size_t)blockDim.x * gridDim.y)
