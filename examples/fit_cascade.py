@@ -3,8 +3,10 @@
     python examples/fit_cascade.py [n_starts]
 
 Builds the project from synthetic data (5 % noise), runs Levenberg-Marquardt from n_starts scattered
-starts at once, then walks 64 Metropolis chains from the best fit.  Everything the loops evaluate -- ODEs,
-forward sensitivities, scale factors, residuals, Jacobians, normal equations -- runs on the device."""
+starts at once, then walks 64 Metropolis chains from the best fit, once with the host sampler (candidates and
+acceptance in numpy around one batched device evaluation per step) and once with sampler='device' (the whole step
+enqueued on the device, one synchronisation at the end).  Everything the loops evaluate -- ODEs, forward
+sensitivities, scale factors, residuals, Jacobians, normal equations -- runs on the device."""
 import os
 import sys
 import time
@@ -38,10 +40,13 @@ def main():
           % (n_starts, dt, fit['n_evaluations'] * 8))
     print("    cost: start median %.1f -> fit median %.3f, best %.3f (truth: %.3f)"
           % (np.median(c0), np.median(fit['cost']), fit['cost'][best], proj.calc_sum_square_residuals(theta_true)))
-    t0 = time.time()
-    ens, ens_F, ratio = ensemble_log_params_batch(proj, np.tile(fit['theta'][best], (64, 1)), steps=200, seeds=1,
-                                                  sing_val_cutoff=1e-4, step_scale=0.3, energy='rss')
-    print("MCMC: 64 chains x 200 steps in %.2f s, acceptance %.2f" % (time.time() - t0, ratio.mean()))
+    chains = dict(seeds=1, sing_val_cutoff=1e-4, step_scale=0.3, energy='rss')
+    start = np.tile(fit['theta'][best], (64, 1))
+    for sampler in ('host', 'device'):
+        ensemble_log_params_batch(proj, start, steps=2, sampler=sampler, **chains)       # warm-up: neither timing pays it
+        t0 = time.time()
+        ens, ens_F, ratio = ensemble_log_params_batch(proj, start, steps=200, sampler=sampler, **chains)
+        print("MCMC (%s sampler): 64 chains x 200 steps in %.2f s, acceptance %.2f" % (sampler, time.time() - t0, ratio.mean()))
     sd = ens[50:].reshape(-1, ens.shape[-1]).std(axis=0)
     names = [n for n, _ in proj.get_ordered_project_params()]
     tight = np.argsort(sd)[:3]

@@ -472,6 +472,34 @@ int sbm_lm_accept(sbm_ctx* ctx, const int32_t* accept_dev, int32_t V, int32_t M,
  * sum over a vector's E trajectories; an integrator budget applies per trajectory).  Device to device, on the stream. */
 int sbm_project_trajectory_steps(sbm_project* project, int32_t V, int32_t* steps_dev);
 
+/* ---- the Metropolis sampler's step (project/ensembles.py, sampler='device') ---- */
+/* Scale-factor entropy of V vectors of simulations (the reference's calc_scale_factors_entropy, base_project.py:854-872,
+ * linear_scale_factor.py:63-81): for every vector v and scale-factor group k, from the project's rows,
+ *     a = sum s^2 / sigma^2,  b = sum s d / sigma^2,  B* = b / a,
+ *     group_entropy[v][k] = log integral du exp(-a / (2 T) (e^u B* - B*)^2 - (u + log B* - mu_k)^2 / (2 sigma_k^2)),
+ *     entropy[v] = T sum_k group_entropy[v][k],
+ * (mu_k, sigma_k): the group's log prior.  The integral is taken by a fixed-node rule as a max-subtracted log-sum-exp
+ * (csrc/sbm_sf_quadrature.hpp): finite where the integrand underflows a double.  Rows without a scale factor take no
+ * part.  entropy[v] = -inf (so that F = +inf: the move is rejected) where a simulation of v is not finite or b / a <= 0
+ * for some group.  A project in which a group has no log prior is refused with SBM_E_ARG.
+ * sims [V][R] in; entropy [V] out; group_entropy [V][G] out, nullable.  Device pointers, the context's stream. */
+int sbm_project_sf_entropy(sbm_project* project, const double* sims_dev, int32_t V, double temperature,
+                           double* entropy_dev, double* group_entropy_dev);
+
+/* Candidate move of C chains: trial = curr + samp z.  samp: V diag(s) of the candidate density, one [q][q] matrix
+ * (per_chain = 0) or [C][q][q]; z [C][q] standard normal draws. */
+int sbm_mh_propose(sbm_ctx* ctx, const double* curr_dev, const double* samp_dev, int32_t per_chain, const double* z_dev,
+                   int32_t C, int32_t q, double* trial_dev);
+
+/* Metropolis rule for C chains: F_trial = 0.5 norms_trial - entropy_trial (entropy_trial NULL: energy 0.5 |r|^2); the
+ * trial point is taken iff status_trial == 0, F_trial is finite and log_u < -(F_trial - F_curr) / T.  Taken points
+ * replace curr and F_curr and count in n_accepted; ens_slot [C][q] and ens_F_slot [C] (nullable) receive the chains'
+ * points and energies after the step. */
+int sbm_mh_accept(sbm_ctx* ctx, const double* norms_trial_dev, const int32_t* status_trial_dev,
+                  const double* entropy_trial_dev, const double* log_u_dev, double temperature, int32_t C, int32_t q,
+                  const double* trial_dev, double* curr_dev, double* F_curr_dev, int32_t* n_accepted_dev,
+                  double* ens_slot_dev, double* ens_F_slot_dev);
+
 /* ---- multi-GPU: the one exchange of the path ----------------------------- */
 /* The path shards by parameter vector with no data-path collective; what every
  * rank may want afterwards is everybody's per-vector ||r||^2 (sbm_residuals_batch's

@@ -9,6 +9,9 @@
 //                     Jacobian (base_project.py:365-391,443-488; project/utils.py:10-89;
 //                     loss_functions/squared_loss/squared_loss_function.py:27-80;
 //                     linear_scale_factor.py:27-42)
+//   k_sf_entropy      scale-factor entropy integrals of a batch of simulations (linear_scale_factor.py:63-81)
+//   k_mh_propose / k_mh_accept   candidate move and Metropolis rule of the multi-chain sampler
+//                     (project/Ensembles.py:193-198, 260-264)
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <stdarg.h>
@@ -20,6 +23,7 @@
 #include <vector>
 
 #include "sbm_plugin.h"
+#include "sbm_sf_quadrature.hpp"
 
 // ---------------------------------------------------------------------------
 // errors
@@ -93,6 +97,9 @@ struct sbm_project {
   DevBuf<int32_t> pmap, sens_col, tgrid_off, grid_len, row_exp, row_tidx, row_var_off, row_vars, row_sf,
       prior_idx, inv_ptr, inv_m, sfp_group;
   DevBuf<double> pfixed, tgrid, row_data, row_sigma, prior_mean, prior_sigma, sfp_mean, sfp_sigma;
+  // log prior of every scale-factor group, [G] (sbm_project_sf_entropy); sf_group_without_prior: first group that has none, or -1
+  DevBuf<double> sfg_mean, sfg_sigma;
+  int sf_group_without_prior = -1;
   // custom observables (postfix programs): see sbm_project_desc
   int n_programs = 0, n_custom_weights = 0;
   DevBuf<int32_t> row_prog, row_w0, prog_base, prog_sub_off, prog_code;
@@ -454,9 +461,14 @@ __global__ void k_fill_grids(const int32_t* __restrict__ tgrid_off, int V, int E
   glen[idx] = tgrid_off[e + 1] - tgrid_off[e];
 }
 
-__device__ __forceinline__ double block_sum(double v, double* red /*[4]*/) {
+__device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+__device__ __forceinline__ double block_sum(double v, double* red /*[4]*/) {
+  v = wave_sum(v);
   const int w = threadIdx.x >> 6;
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[w] = v;
@@ -999,6 +1011,15 @@ extern "C" int sbm_project_load(sbm_model* m, const sbm_project_desc* d, sbm_pro
   bad |= upload(p->sfp_group, d->sf_prior_group, (size_t)NSP, s);
   bad |= upload(p->sfp_mean, d->sf_prior_mean, (size_t)NSP, s);
   bad |= upload(p->sfp_sigma, d->sf_prior_sigma, (size_t)NSP, s);
+  std::vector<double> sfg_mean((size_t)(G > 0 ? G : 1), 0.0), sfg_sigma((size_t)(G > 0 ? G : 1), 0.0);
+  for (int k = 0; k < NSP; ++k) {
+    sfg_mean[d->sf_prior_group[k]] = d->sf_prior_mean[k];
+    sfg_sigma[d->sf_prior_group[k]] = d->sf_prior_sigma[k];
+  }
+  for (int k = G - 1; k >= 0; --k)
+    if (!(sfg_sigma[k] > 0.0)) p->sf_group_without_prior = k;
+  bad |= upload(p->sfg_mean, sfg_mean.data(), (size_t)G, s);
+  bad |= upload(p->sfg_sigma, sfg_sigma.data(), (size_t)G, s);
   bad |= upload(p->inv_ptr, inv_ptr.data(), inv_ptr.size(), s);
   bad |= upload(p->inv_m, inv_m.data(), inv_m.size(), s);
   p->n_programs = NPG;
@@ -1028,7 +1049,7 @@ extern "C" int sbm_project_unload(sbm_project* p) {
   p->row_tidx.release(); p->row_var_off.release(); p->row_vars.release(); p->row_sf.release(); p->prior_idx.release();
   p->inv_ptr.release(); p->inv_m.release(); p->pfixed.release(); p->tgrid.release(); p->row_data.release();
   p->row_sigma.release(); p->prior_mean.release(); p->prior_sigma.release();
-  p->sfp_group.release(); p->sfp_mean.release(); p->sfp_sigma.release();
+  p->sfp_group.release(); p->sfp_mean.release(); p->sfp_sigma.release(); p->sfg_mean.release(); p->sfg_sigma.release();
   p->row_prog.release(); p->row_w0.release(); p->prog_base.release(); p->prog_sub_off.release(); p->prog_code.release();
   p->prog_const.release(); p->row_time.release();
   p->P.release(); p->Y.release(); p->S.release(); p->sims.release(); p->sf.release();
@@ -1891,6 +1912,156 @@ extern "C" int sbm_lm_accept(sbm_ctx* ctx, const int32_t* accept, int32_t V, int
   const int ny = (int)(((size_t)M * q / 2 + 256 * 8 - 1) / (256 * 8));       // ~8 double2 per thread
   hipLaunchKernelGGL(k_lm_accept, dim3(V, ny < 1 ? 1 : (ny > 64 ? 64 : ny)), dim3(256), 0, ctx->stream, accept, q, M, trial, r_trial,
                      J_trial, norms_trial, theta, r, J, cost);
+  SBM_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The Metropolis sampler's step on the device (project/ensembles.py, sampler='device'): scale-factor entropy of the
+// trial simulations, candidate move, acceptance.  Between sbm_mh_propose, sbm_residuals_batch, sbm_project_sf_entropy
+// and sbm_mh_accept no number goes through the host.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+// One workgroup of four wavefronts per vector; wavefront w takes the groups w, w + 4, ...  For a group the rows go along
+// the lanes (a = sum s^2 / sigma^2, b = sum s d / sigma^2 by a butterfly), then the panels of the quadrature rule
+// (sbm_sf_quadrature.hpp) do: lane l integrates panels l and l + 64 and the wavefront combines the 64 partial
+// log-sum-exps.  LDS: the G group values of the vector, summed in group order by one thread, so that the entropy does
+// not depend on which wavefront finished first.
+__global__ void __launch_bounds__(256) k_sf_entropy(const double* __restrict__ sims, int R, int G,
+                                                    const double* __restrict__ row_data, const double* __restrict__ row_sigma,
+                                                    const int32_t* __restrict__ row_sf, const double* __restrict__ sfg_mean,
+                                                    const double* __restrict__ sfg_sigma, double temperature,
+                                                    double* __restrict__ entropy, double* __restrict__ group_entropy) {
+  extern __shared__ double s_group[];   // [G]
+  const int v = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const double* sv = sims + (size_t)v * R;
+  for (int k = wave; k < G; k += 4) {
+    double a = 0.0, b = 0.0;
+    int bad = 0;
+    for (int r = lane; r < R; r += 64) {
+      const double s = sv[r];
+      bad |= !(fabs(s) <= 1.79769313486231570815e308);       // any row of the vector, scale factor or not
+      if (row_sf[r] == k) {
+        const double w = 1.0 / (row_sigma[r] * row_sigma[r]);
+        a = fma(s * s, w, a);
+        b = fma(s * row_data[r], w, b);
+      }
+    }
+    a = wave_sum(a);
+    b = wave_sum(b);
+    bad = __any(bad);
+    double alpha = 0.0, c = 0.0, val = -__builtin_inf();
+    if (!bad && sbm_sfq_params(a, b, sfg_mean[k], temperature, &alpha, &c)) {
+      sbm_sfq_plan q;
+      sbm_sfq_make_plan(alpha, c, sfg_sigma[k], &q);         // (the same on every lane)
+      double m = -__builtin_inf(), sum = 0.0;
+      sbm_sfq_add_panel(q, lane, &m, &sum);
+      sbm_sfq_add_panel(q, lane + 64, &m, &sum);
+      const double mw = wave_max(m);
+      const double tot = wave_sum(m > -__builtin_inf() ? sum * exp(m - mw) : 0.0);
+      val = mw + log(tot);                                    // (no panel at all: -inf + log 0 = -inf)
+    }
+    if (lane == 0) {
+      s_group[k] = val;
+      if (group_entropy) group_entropy[(size_t)v * G + k] = val;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double e = 0.0;
+    for (int k = 0; k < G; ++k) e += temperature * s_group[k];
+    entropy[v] = e == e ? e : -__builtin_inf();
+  }
+}
+
+extern "C" int sbm_project_sf_entropy(sbm_project* p, const double* sims, int32_t V, double temperature, double* entropy,
+                                      double* group_entropy) {
+  if (!p || !sims || !entropy) return sbm_fail(SBM_E_ARG, "sbm_project_sf_entropy: NULL argument");
+  if (V < 0) return sbm_fail(SBM_E_ARG, "sbm_project_sf_entropy: V < 0");
+  if (!(temperature > 0.0)) return sbm_fail(SBM_E_ARG, "sbm_project_sf_entropy: temperature must be positive");
+  if (p->G <= 0) return sbm_fail(SBM_E_ARG, "sbm_project_sf_entropy: the project has no scale factors");
+  if (p->sf_group_without_prior >= 0)
+    return sbm_fail(SBM_E_ARG, "sbm_project_sf_entropy: scale factor entropy needs a log prior on every scale factor (group %d has none)",
+                    p->sf_group_without_prior);
+  if (V == 0) return 0;
+  SBM_HIP(hipSetDevice(p->model->ctx->device));
+  hipLaunchKernelGGL(k_sf_entropy, dim3(V), dim3(256), sizeof(double) * (size_t)p->G, p->model->ctx->stream, sims, p->R, p->G,
+                     p->row_data.p, p->row_sigma.p, p->row_sf.p, p->sfg_mean.p, p->sfg_sigma.p, temperature, entropy, group_entropy);
+  SBM_HIP(hipGetLastError());
+  return 0;
+}
+
+// trial = curr + samp z: one thread per (chain, component); samp is one [q][q] matrix or one per chain
+__global__ void __launch_bounds__(256) k_mh_propose(const double* __restrict__ curr, const double* __restrict__ samp, int per_chain,
+                                                    const double* __restrict__ z, int C, int q, double* __restrict__ trial) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (size_t)C * q) return;
+  const size_t c = idx / q;
+  const int i = (int)(idx % q);
+  const double* row = samp + (per_chain ? c * q * q : 0) + (size_t)i * q;
+  const double* zc = z + c * q;
+  double d = 0.0;
+  for (int j = 0; j < q; ++j) d = fma(row[j], zc[j], d);
+  trial[idx] = curr[idx] + d;
+}
+
+extern "C" int sbm_mh_propose(sbm_ctx* ctx, const double* curr, const double* samp, int32_t per_chain, const double* z, int32_t C,
+                              int32_t q, double* trial) {
+  if (!ctx || !curr || !samp || !z || !trial) return sbm_fail(SBM_E_ARG, "sbm_mh_propose: NULL argument");
+  if (C < 0 || q <= 0) return sbm_fail(SBM_E_ARG, "sbm_mh_propose: bad sizes C=%d q=%d", C, q);
+  if (C == 0) return 0;
+  SBM_HIP(hipSetDevice(ctx->device));
+  const size_t n = (size_t)C * q;
+  hipLaunchKernelGGL(k_mh_propose, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, curr, samp, per_chain, z, C, q, trial);
+  SBM_HIP(hipGetLastError());
+  return 0;
+}
+
+// One wavefront per chain: every lane reads the chain's scalars and takes the same decision, the lanes stride over the
+// q components, lane 0 writes the scalars.
+__global__ void __launch_bounds__(256) k_mh_accept(const double* __restrict__ norms_t, const int32_t* __restrict__ status_t,
+                                                   const double* __restrict__ entropy_t, const double* __restrict__ log_u,
+                                                   double temperature, int C, int q, const double* __restrict__ trial,
+                                                   double* __restrict__ curr, double* __restrict__ F_curr,
+                                                   int32_t* __restrict__ n_accepted, double* __restrict__ ens_slot,
+                                                   double* __restrict__ ens_F_slot) {
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (c >= C) return;
+  const double Fc = F_curr[c];
+  const double Ft = 0.5 * norms_t[c] - (entropy_t ? entropy_t[c] : 0.0);
+  const bool finite = fabs(Ft) <= 1.79769313486231570815e308;       // (false for NaN)
+  const bool acc = status_t[c] == 0 && finite && log_u[c] < -(Ft - Fc) / temperature;
+  for (int i = lane; i < q; i += 64) {
+    const size_t e = (size_t)c * q + i;
+    const double x = acc ? trial[e] : curr[e];
+    if (acc) curr[e] = x;
+    if (ens_slot) ens_slot[e] = x;
+  }
+  if (lane == 0) {
+    if (acc) {
+      F_curr[c] = Ft;
+      n_accepted[c] += 1;
+    }
+    if (ens_F_slot) ens_F_slot[c] = acc ? Ft : Fc;
+  }
+}
+
+extern "C" int sbm_mh_accept(sbm_ctx* ctx, const double* norms_trial, const int32_t* status_trial, const double* entropy_trial,
+                             const double* log_u, double temperature, int32_t C, int32_t q, const double* trial, double* curr,
+                             double* F_curr, int32_t* n_accepted, double* ens_slot, double* ens_F_slot) {
+  if (!ctx || !norms_trial || !status_trial || !log_u || !trial || !curr || !F_curr || !n_accepted)
+    return sbm_fail(SBM_E_ARG, "sbm_mh_accept: NULL argument");
+  if (C < 0 || q <= 0) return sbm_fail(SBM_E_ARG, "sbm_mh_accept: bad sizes C=%d q=%d", C, q);
+  if (!(temperature > 0.0)) return sbm_fail(SBM_E_ARG, "sbm_mh_accept: temperature must be positive");
+  if (C == 0) return 0;
+  SBM_HIP(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(k_mh_accept, dim3((C + 3) / 4), dim3(256), 0, ctx->stream, norms_trial, status_trial, entropy_trial, log_u,
+                     temperature, C, q, trial, curr, F_curr, n_accepted, ens_slot, ens_F_slot);
   SBM_HIP(hipGetLastError());
   return 0;
 }

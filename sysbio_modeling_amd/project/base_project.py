@@ -718,7 +718,7 @@ class Project(object):
         V, q = th.shape
         R = self._n_residuals
         RT = self.n_total_rows
-        G = len(self._loss_function.groups) if hasattr(self._loss_function, 'groups') else 0
+        G = self._n_sf_groups()
         f64, i32 = torch.float64, torch.int32
         out = {'residuals': torch.empty((V, RT), dtype=f64, device=dev),
                'sims': torch.empty((V, R), dtype=f64, device=dev),
@@ -845,8 +845,56 @@ class Project(object):
         rss = self.calc_sum_square_residuals(project_param_vector)
         return rss - self.calc_scale_factors_entropy(temperature)
 
-    def free_energy_batch(self, thetas, temperature=1, **integrator_overrides):
-        """free_energy for V parameter vectors: one batched device evaluation, then the quadratures."""
+    def _n_sf_groups(self):
+        return len(self._loss_function.groups) if hasattr(self._loss_function, 'groups') else 0
+
+    def _require_scale_factor_priors(self):
+        for sf in self._loss_function._scale_factors.values():
+            if sf.log_prior is None:
+                raise ValueError("scale factor entropy needs a log prior on every scale factor "
+                                 "(set_scale_factor_log_prior)")
+
+    def scale_factors_entropy_batch(self, sims, temperature=1.0, group_entropy=False):
+        """``calc_scale_factors_entropy`` for V vectors of simulations on the device (``sbm_project_sf_entropy``): the
+        row sums and the integrals of every (vector, group) pair in one launch, by a fixed-node quadrature rule taken as
+        a log-sum-exp (csrc/sbm_sf_quadrature.hpp).  ``sims`` (V, n_project_residuals), numpy or torch CUDA; the result
+        (V,) is of the same kind, and with ``group_entropy=True`` a pair with the (V, G) log-integrals.  -inf where a
+        simulation is not finite or a group's best-fit scale factor is not positive (the host method gives NaN there).
+        Every group needs a log prior: ValueError otherwise, as from the host method."""
+        import torch
+        self._require_scale_factor_priors()
+        proj = self._device()
+        dev = torch.device('cuda', self._model.device_model.ctx.device)
+        as_torch = isinstance(sims, torch.Tensor)
+        sd = sims if as_torch else torch.from_numpy(np.atleast_2d(_as_f64(sims)))
+        sd = sd.to(device=dev, dtype=torch.float64)
+        if sd.dim() == 1:
+            sd = sd.unsqueeze(0)
+        sd = sd.contiguous()
+        if sd.shape[1] != self._n_residuals:
+            raise ValueError("sims has %d columns, the project has %d measurement rows" % (sd.shape[1], self._n_residuals))
+        V, G = sd.shape[0], self._n_sf_groups()
+        ent = torch.empty((V,), dtype=torch.float64, device=dev)
+        grp = torch.empty((V, G), dtype=torch.float64, device=dev) if group_entropy else None
+        _lib.check(_lib.load_library().sbm_project_sf_entropy(proj, _lib.dev_ptr(sd), V, float(temperature), _lib.dev_ptr(ent),
+                                                              _lib.dev_ptr(grp)), 'sbm_project_sf_entropy')
+        if not as_torch:
+            torch.cuda.synchronize(dev)
+            ent = ent.cpu().numpy()
+            grp = grp.cpu().numpy() if group_entropy else None
+        return (ent, grp) if group_entropy else ent
+
+    def free_energy_batch(self, thetas, temperature=1, device=False, **integrator_overrides):
+        """free_energy for V parameter vectors: one batched device evaluation, then the quadratures -- on the host, one
+        ``scipy.integrate.quad`` per vector and group (``device=False``, the default), or on the device
+        (``device=True``: ``scale_factors_entropy_batch``; +inf where that gives -inf)."""
+        if device:
+            import torch
+            th, as_torch = self._theta_dev(thetas)
+            res = self.evaluate_batch(th, want=('sims', 'norms', 'status'), **integrator_overrides)
+            out = 0.5 * res['norms'] - self.scale_factors_entropy_batch(res['sims'], temperature)
+            out = torch.where(torch.isfinite(out) & (res['status'] == 0), out, torch.full_like(out, float('inf')))
+            return out if as_torch else out.cpu().numpy()
         res = self.evaluate_batch(thetas, **integrator_overrides)
         out = 0.5 * res['norms']
         for v in range(len(out)):
