@@ -5,7 +5,8 @@
 Builds the project from synthetic data (5 % noise), runs Levenberg-Marquardt from n_starts scattered
 starts at once, then walks 64 Metropolis chains from the best fit, once with the host sampler (candidates and
 acceptance in numpy around one batched device evaluation per step) and once with sampler='device' (the whole step
-enqueued on the device, one synchronisation at the end).  Everything the loops evaluate -- ODEs, forward
+enqueued on the device, one synchronisation at the end), and turns the sampled ensemble into the 95 % band of one scaled
+observable (trajectories of all members, then mean / sd / quantiles over the members on the device).  Everything the loops evaluate -- ODEs, forward
 sensitivities, scale factors, residuals, Jacobians, normal equations -- runs on the device."""
 import os
 import sys
@@ -17,7 +18,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sysbio_modeling_amd import models_zoo
 from sysbio_modeling_amd.model import OdeModel
-from sysbio_modeling_amd.project.ensembles import ensemble_log_params_batch
+from sysbio_modeling_amd.project.ensembles import ensemble_log_params_batch, ensemble_predictions
 from sysbio_modeling_amd.symbolic import zoo_model
 
 
@@ -53,6 +54,18 @@ def main():
     loose = np.argsort(sd)[-3:]
     print("    best constrained (log-units sd): " + ", ".join("%s %.3f" % (names[i], sd[i]) for i in tight))
     print("    sloppiest:                       " + ", ".join("%s %.3f" % (names[i], sd[i]) for i in loose))
+    # predictions with uncertainty: the chains after burn-in, (n_kept, C, q) as the sampler returns them
+    times = np.linspace(0.0, 100.0, 201)
+    t0 = time.time()
+    pred = ensemble_predictions(proj, times, ens[50:], quantiles=(0.025, 0.5, 0.975))
+    first = next(iter(pred))
+    band = pred[first]['measures']
+    k = band['names'].index('s19')
+    print("predictions: %d members x %d experiments x %d times in %.2f s (%d members usable); 95 %% band of scaled s19 in %s:"
+          % (ens[50:].shape[0] * ens.shape[1], len(pred), len(times), time.time() - t0, band['n_used'], first))
+    for i in (20, 60, 100, 200):
+        lo, med, hi = band['quantiles'][:, i, k]
+        print("    t = %5.1f   %.4f  [%.4f, %.4f]" % (times[i], med, lo, hi))
 
 
 if __name__ == '__main__':

@@ -500,6 +500,29 @@ int sbm_mh_accept(sbm_ctx* ctx, const double* norms_trial_dev, const int32_t* st
                   const double* trial_dev, double* curr_dev, double* F_curr_dev, int32_t* n_accepted_dev,
                   double* ens_slot_dev, double* ens_F_slot_dev);
 
+/* ---- ensemble predictions: statistics over the member axis ------------------ */
+/* replaces traj_ensemble_stats / traj_ensemble_quantiles / the NaN filter of few_ensemble_trajs
+ * (project/Ensembles.py:277-308, 335-361) for V members at once.
+ * values   [V][L]   device; L = n_t * n_cols, the layout sbm_simulate_batch writes
+ * status   [V]      device, nullable: a member with status != 0 is left out
+ * A member with ANY non-finite value among its L entries is left out as a whole.
+ * levels   [Q]      HOST, each in [0, 1]; Q may be 0 (at most 64 levels per call)
+ * mean, sd [L]      device out, each nullable; sd is the population value (ddof = 0, scipy.std)
+ * quant    [Q][L]   device out (nullable iff Q == 0)
+ * used     [V]      device out, nullable: 1 = member took part
+ * n_used   [1]      device out, nullable
+ * With n used members and the sorted column x_(0..n-1), level q gives idx = q (n - 1), b = floor(idx), a = ceil(idx) and
+ * x_(b) + (idx - b) (x_(a) - x_(b)) -- x_(b) itself when a == b -- numpy's 'linear' rule, what scipy.stats.mstats.mquantiles
+ * computes in the reference (:350-358).  Which members take part is decided once, so every column sees the same n;
+ * n == 0: every output entry is NaN and n_used = 0 (no error); n == 1: sd = 0 and every quantile is the value.
+ * A column is sorted in the LDS of one workgroup: V <= SBM_ENSEMBLE_MAX_MEMBERS, more is SBM_E_ARG (no host fallback).
+ * Asynchronous on the context's stream; the context keeps two integers per member of device scratch, grown on demand
+ * and freed with the context. */
+#define SBM_ENSEMBLE_MAX_MEMBERS 16384
+int sbm_ensemble_stats(sbm_ctx* ctx, const double* values_dev, const int32_t* status_dev, int32_t V, int64_t L,
+                       const double* levels, int32_t Q, double* mean_dev, double* sd_dev, double* quant_dev,
+                       int32_t* used_dev, int32_t* n_used_dev);
+
 /* ---- multi-GPU: the one exchange of the path ----------------------------- */
 /* The path shards by parameter vector with no data-path collective; what every
  * rank may want afterwards is everybody's per-vector ||r||^2 (sbm_residuals_batch's

@@ -12,6 +12,8 @@
 //   k_sf_entropy      scale-factor entropy integrals of a batch of simulations (linear_scale_factor.py:63-81)
 //   k_mh_propose / k_mh_accept   candidate move and Metropolis rule of the multi-chain sampler
 //                     (project/Ensembles.py:193-198, 260-264)
+//   k_ens_*           statistics over the member axis of an ensemble of trajectories (sbm_ensemble_stats.hpp;
+//                     project/Ensembles.py:277-308, 335-361)
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <stdarg.h>
@@ -24,6 +26,7 @@
 
 #include "sbm_plugin.h"
 #include "sbm_sf_quadrature.hpp"
+#include "sbm_ensemble_stats.hpp"
 
 // ---------------------------------------------------------------------------
 // errors
@@ -49,12 +52,6 @@ enum { SBM_E_ARG = -1, SBM_E_HIP = -2, SBM_E_PLUGIN = -3 };
 // ---------------------------------------------------------------------------
 // objects
 // ---------------------------------------------------------------------------
-struct sbm_ctx {
-  int device;
-  hipStream_t stream;
-  bool own_stream;
-};
-
 struct sbm_model;
 
 template <class T>
@@ -75,6 +72,14 @@ struct DevBuf {
     p = nullptr;
     n = 0;
   }
+};
+
+struct sbm_ctx {
+  int device;
+  hipStream_t stream;
+  bool own_stream;
+  // sbm_ensemble_stats: validity flags [V], used members [V], their number [1]
+  DevBuf<int32_t> ens_flag, ens_idx, ens_n;
 };
 
 struct sbm_model {
@@ -139,6 +144,9 @@ extern "C" int sbm_ctx_create(int device, void* stream, sbm_ctx** out) {
 extern "C" int sbm_ctx_destroy(sbm_ctx* c) {
   if (!c) return 0;
   if (c->own_stream) (void)hipStreamDestroy(c->stream);
+  c->ens_flag.release();
+  c->ens_idx.release();
+  c->ens_n.release();
   delete c;
   return 0;
 }
@@ -2062,6 +2070,73 @@ extern "C" int sbm_mh_accept(sbm_ctx* ctx, const double* norms_trial, const int3
   SBM_HIP(hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_mh_accept, dim3((C + 3) / 4), dim3(256), 0, ctx->stream, norms_trial, status_trial, entropy_trial, log_u,
                      temperature, C, q, trial, curr, F_curr, n_accepted, ens_slot, ens_F_slot);
+  SBM_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Ensemble predictions: statistics over the member axis (kernels and the work split: sbm_ensemble_stats.hpp).
+// ---------------------------------------------------------------------------------------------
+extern "C" int sbm_ensemble_stats(sbm_ctx* ctx, const double* values, const int32_t* status, int32_t V, int64_t L,
+                                  const double* levels, int32_t Q, double* mean, double* sd, double* quant, int32_t* used,
+                                  int32_t* n_used) {
+  if (!ctx || (!values && V > 0 && L > 0)) return sbm_fail(SBM_E_ARG, "sbm_ensemble_stats: NULL argument");
+  if (V < 0 || L < 0 || Q < 0) return sbm_fail(SBM_E_ARG, "sbm_ensemble_stats: bad sizes V=%d L=%lld Q=%d", V, (long long)L, Q);
+  if (V > SBM_ENSEMBLE_MAX_MEMBERS)
+    return sbm_fail(SBM_E_ARG, "sbm_ensemble_stats: %d members; a column is sorted in the LDS of one workgroup, which holds "
+                    "SBM_ENSEMBLE_MAX_MEMBERS = %d", V, SBM_ENSEMBLE_MAX_MEMBERS);
+  if (Q > SBM_ENS_MAX_LEVELS) return sbm_fail(SBM_E_ARG, "sbm_ensemble_stats: %d quantile levels (at most %d per call)", Q, SBM_ENS_MAX_LEVELS);
+  if (Q > 0 && (!levels || !quant)) return sbm_fail(SBM_E_ARG, "sbm_ensemble_stats: Q > 0 needs levels and quant");
+  sbm_ens_levels lv;
+  memset(&lv, 0, sizeof(lv));
+  for (int i = 0; i < Q; ++i) {
+    if (!(levels[i] >= 0.0 && levels[i] <= 1.0)) return sbm_fail(SBM_E_ARG, "sbm_ensemble_stats: level %d = %g is not in [0, 1]", i, levels[i]);
+    lv.q[i] = levels[i];
+  }
+  SBM_HIP(hipSetDevice(ctx->device));
+  const size_t nv = (size_t)(V > 0 ? V : 1);
+  if (ctx->ens_flag.reserve(nv) || ctx->ens_idx.reserve(nv) || ctx->ens_n.reserve(1))
+    return sbm_fail(SBM_E_HIP, "sbm_ensemble_stats: out of device memory");
+  hipStream_t s = ctx->stream;
+  if (V > 0) hipLaunchKernelGGL(k_ens_valid, dim3((V + 3) / 4), dim3(256), 0, s, values, status, V, L, ctx->ens_flag.p);
+  hipLaunchKernelGGL(k_ens_compact, dim3(1), dim3(1024), 0, s, ctx->ens_flag.p, V, ctx->ens_idx.p, ctx->ens_n.p, used, n_used);
+  SBM_HIP(hipGetLastError());
+  if (L == 0 || (!mean && !sd && Q == 0)) return 0;
+
+  int slots = 1;
+  while (slots < V) slots <<= 1;
+  const bool wide = slots >= SBM_ENS_PACK_SLOTS;
+  int C = 1;
+  if (!wide) {
+    C = SBM_ENS_PACK_SLOTS / slots;
+    if (C > SBM_ENS_PACK_MAX_COLS) C = SBM_ENS_PACK_MAX_COLS;
+  }
+  const int threads = wide ? 1024 : 256;
+  const size_t lds = sizeof(double) * ((size_t)C * (size_t)(C > 1 ? slots + 1 : slots) + (size_t)threads / 64);
+  if (lds > 64 * 1024)
+    SBM_HIP(hipFuncSetAttribute((const void*)k_ens_columns<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  sbm_ens_cols_args a;
+  a.n_ptr = ctx->ens_n.p;
+  a.L = L;
+  a.slots = slots;
+  a.cols_per_block = C;
+  a.Q = Q;
+  a.mean = mean;
+  a.sd = sd;
+  a.quant = quant;
+  a.values = values;
+  a.idx = ctx->ens_idx.p;
+  const int64_t chunk = (int64_t)C * 0x40000000ll;      // columns of one launch: the grid's x extent
+  for (int64_t j0 = 0; j0 < L; j0 += chunk) {
+    const int64_t nc = L - j0 < chunk ? L - j0 : chunk;
+    a.j0 = j0;
+    a.n_cols = (int32_t)nc;
+    const unsigned blocks = (unsigned)((nc + C - 1) / C);
+    if (wide)
+      hipLaunchKernelGGL(k_ens_columns<1024>, dim3(blocks), dim3(1024), lds, s, a, lv);
+    else
+      hipLaunchKernelGGL(k_ens_columns<256>, dim3(blocks), dim3(256), lds, s, a, lv);
+  }
   SBM_HIP(hipGetLastError());
   return 0;
 }

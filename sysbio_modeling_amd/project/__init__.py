@@ -1,4 +1,7 @@
 from .base_project import Project
 from . import utils
+from .ensembles import (EnsembleTrajectories, ensemble_predictions, ensemble_trajs, net_ensemble_trajs,
+                        traj_ensemble_quantiles, traj_ensemble_stats)
 
-__all__ = ['Project', 'utils']
+__all__ = ['Project', 'utils', 'EnsembleTrajectories', 'ensemble_predictions', 'ensemble_trajs', 'net_ensemble_trajs',
+           'traj_ensemble_quantiles', 'traj_ensemble_stats']
