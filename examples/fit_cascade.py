@@ -4,8 +4,9 @@
 
 Builds the project from synthetic data (5 % noise), runs Levenberg-Marquardt from n_starts scattered
 starts at once, then walks 64 Metropolis chains from the best fit, once with the host sampler (candidates and
-acceptance in numpy around one batched device evaluation per step) and once with sampler='device' (the whole step
-enqueued on the device, one synchronisation at the end), and turns the sampled ensemble into the 95 % band of one scaled
+acceptance in numpy around one batched device evaluation per step), once with sampler='device' (the whole step
+enqueued on the device, one synchronisation at the end) and once with sampler='device_recalc' (the reference's second
+algorithm on the device: every chain's candidate from the Hessian at its own point, Metropolis-Hastings acceptance), and turns the sampled ensemble into the 95 % band of one scaled
 observable (trajectories of all members, then mean / sd / quantiles over the members on the device).  Everything the loops evaluate -- ODEs, forward
 sensitivities, scale factors, residuals, Jacobians, normal equations -- runs on the device."""
 import os
@@ -48,6 +49,11 @@ def main():
         t0 = time.time()
         ens, ens_F, ratio = ensemble_log_params_batch(proj, start, steps=200, sampler=sampler, **chains)
         print("MCMC (%s sampler): 64 chains x 200 steps in %.2f s, acceptance %.2f" % (sampler, time.time() - t0, ratio.mean()))
+    ensemble_log_params_batch(proj, start, steps=2, sampler='device_recalc', **chains)
+    t0 = time.time()
+    _, _, ratio_r = ensemble_log_params_batch(proj, start, steps=200, sampler='device_recalc', **chains)
+    print("MCMC (device_recalc sampler, Hessian per chain and step): 64 chains x 200 steps in %.2f s, acceptance %.2f"
+          % (time.time() - t0, ratio_r.mean()))
     sd = ens[50:].reshape(-1, ens.shape[-1]).std(axis=0)
     names = [n for n, _ in proj.get_ordered_project_params()]
     tight = np.argsort(sd)[:3]

@@ -500,6 +500,49 @@ int sbm_mh_accept(sbm_ctx* ctx, const double* norms_trial_dev, const int32_t* st
                   const double* trial_dev, double* curr_dev, double* F_curr_dev, int32_t* n_accepted_dev,
                   double* ens_slot_dev, double* ens_F_slot_dev);
 
+/* ---- the sampler's second algorithm (project/ensembles.py, sampler='device_recalc') ---- */
+/* Axes of the Gaussian candidate density from a Hessian per chain (the reference's _sampling_matrix, Ensembles.py:226-258,
+ * SloppyCell's recipe), for C chains in one launch.  Exactly one of J and H is non-NULL:
+ *   J [C][M][q]           H_c = sum_m (row_scale[m] J[c][m][:]) (x) (the same): the Gauss-Newton Hessian; row_scale [M]
+ *                         nullable, as in sbm_lm_trust_step_ex (a reference_compat Jacobian is not divided by sigma)
+ *   H [q][q] (per_chain_H = 0) or [C][q][q]: used as (H + H^T) / 2; M is ignored
+ * With A = H / 2, its eigenvalues in ascending SIGNED order (as LAPACK's symmetric solvers return them) and then replaced by
+ * their absolute values a_i, c = cutoff max a, n_eff = sum_i min(a_i / c, 1) (= q when c == 0):
+ *   eig  [C][q]      a
+ *   V    [C][q][q]   eigenvectors in the columns, V[c][r][i] = component r of eigenvector i
+ *   s    [C][q]      step_scale sqrt(temperature / n_eff) / sqrt(max(a_i, c, DBL_MIN))
+ *   samp [C][q][q]   V diag(s): the candidate move is samp z, z standard normal (sbm_mh_propose, per_chain = 1)
+ * each nullable, and status [C]: 0, or 1 where an input entry is not finite or the iteration did not converge (that
+ * chain's V and samp are then zero, its s and eig NaN; the other chains are not affected).
+ * Sign convention: in every eigenvector the component of largest magnitude is positive; among components of equal
+ * magnitude the one with the lowest index decides.  A chain replayed with the same normal draws depends on it.
+ * The eigenvalues come from a cyclic Jacobi iteration that stops when every pair satisfies
+ * |a_pq| <= DBL_EPSILON sqrt(|a_pp a_qq|) -- relative to the two diagonal entries, so that the small eigenvalues of a
+ * sloppy Hessian, whose 1 / sqrt are the long step lengths, keep their leading digits -- capped at 40 sweeps.
+ * One 256-thread workgroup per chain with A and V in LDS: q <= SBM_SAMPLING_AXES_MAX_Q, more is SBM_E_ARG.
+ * cutoff >= 0, temperature > 0, step_scale > 0.  Device pointers; enqueued on the context's stream. */
+#define SBM_SAMPLING_AXES_MAX_Q 96
+int sbm_sampling_axes(sbm_ctx* ctx, const double* J_dev, const double* row_scale_dev, const double* H_dev,
+                      int32_t per_chain_H, int32_t C, int32_t M, int32_t q, double cutoff, double temperature,
+                      double step_scale, double* eig_dev, double* V_dev, double* s_dev, double* samp_dev,
+                      int32_t* status_dev);
+
+/* Metropolis-Hastings rule for C chains whose candidate density depends on the point (the reference's
+ * _accept_move_recalc_alg, Ensembles.py:200-224).  The arguments of sbm_mh_accept, then the axes of the candidate density at
+ * the current points (in / out) and at the trial points (in), as sbm_sampling_axes returns them, and that call's status.
+ * With d = trial - curr and log q(d; V, s) = -0.5 |V^T d / s|^2 - sum log s the trial point is taken iff
+ * status_trial == 0, axes_status_trial == 0, F_trial is finite and
+ *     log_u < -(F_trial - F_curr) / T + log q(-d; V_trial, s_trial) - log q(d; V_curr, s_curr).
+ * A taken point replaces curr and F_curr, counts in n_accepted, and its axes (V, s, samp) replace the current ones;
+ * ens_slot / ens_F_slot as in sbm_mh_accept.  One workgroup per chain. */
+int sbm_mh_accept_hastings(sbm_ctx* ctx, const double* norms_trial_dev, const int32_t* status_trial_dev,
+                           const double* entropy_trial_dev, const double* log_u_dev, double temperature, int32_t C,
+                           int32_t q, const double* trial_dev, double* curr_dev, double* F_curr_dev,
+                           int32_t* n_accepted_dev, double* ens_slot_dev, double* ens_F_slot_dev, double* V_curr_dev,
+                           double* s_curr_dev, double* samp_curr_dev, const double* V_trial_dev,
+                           const double* s_trial_dev, const double* samp_trial_dev,
+                           const int32_t* axes_status_trial_dev);
+
 /* ---- ensemble predictions: statistics over the member axis ------------------ */
 /* replaces traj_ensemble_stats / traj_ensemble_quantiles / the NaN filter of few_ensemble_trajs
  * (project/Ensembles.py:277-308, 335-361) for V members at once.

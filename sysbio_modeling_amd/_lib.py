@@ -24,6 +24,7 @@ SBM_IMPLICIT_ADAPTIVE = 4
 SBM_IMPLICIT_EXTRAP = 6
 IMPLICIT_MAX_NV = 128     # include/sbm.h: SBM_IMPLICIT_MAX_NV
 ENSEMBLE_MAX_MEMBERS = 16384     # include/sbm.h: SBM_ENSEMBLE_MAX_MEMBERS
+SAMPLING_AXES_MAX_Q = 96         # include/sbm.h: SBM_SAMPLING_AXES_MAX_Q
 ENSEMBLE_MAX_LEVELS = 64         # quantile levels per sbm_ensemble_stats call
 STATUS_NAMES = {0: 'ok', 1: 'max_steps', 2: 'non_finite', 3: 'step_underflow', 4: 'newton_fail',
                 5: 'tolerance_not_reached'}
@@ -101,6 +102,10 @@ SIGNATURES = {
     'sbm_project_sf_entropy': (ctypes.c_int, [_vp, _vp, _i32, ctypes.c_double, _vp, _vp]),
     'sbm_mh_propose': (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp]),
     'sbm_mh_accept': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sbm_sampling_axes': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.c_double, ctypes.c_double,
+                                         ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
+    'sbm_mh_accept_hastings': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sbm_project_trajectory_steps': (ctypes.c_int, [_vp, _i32, _vp]),
     'sbm_ensemble_stats': (ctypes.c_int, [_vp, _vp, _vp, _i32, ctypes.c_int64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     'sbm_loss_eval_host': (ctypes.c_int, [_vp, ctypes.POINTER(LossDesc), _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -116,7 +116,8 @@ def _locked_build(target, cmd_for, sources, what, force=False):
 
 
 def _core_sources():
-    srcs = [os.path.join(CSRC_DIR, f) for f in ('sbm_core.hip', 'sbm_plugin.h', 'sbm_sf_quadrature.hpp', 'sbm_ensemble_stats.hpp')]
+    srcs = [os.path.join(CSRC_DIR, f) for f in ('sbm_core.hip', 'sbm_plugin.h', 'sbm_sf_quadrature.hpp', 'sbm_ensemble_stats.hpp',
+                                                  'sbm_sampling_axes.hpp')]
     srcs.append(os.path.join(REPO_DIR, 'include', 'sbm.h'))
     return srcs
 

@@ -12,6 +12,9 @@
 //   k_sf_entropy      scale-factor entropy integrals of a batch of simulations (linear_scale_factor.py:63-81)
 //   k_mh_propose / k_mh_accept   candidate move and Metropolis rule of the multi-chain sampler
 //                     (project/Ensembles.py:193-198, 260-264)
+//   k_sampling_axes / k_mh_accept_hastings   per-chain Hessian axes (batched Jacobi eigensolver + SloppyCell's clipping
+//                     recipe) and the Metropolis-Hastings rule of the sampler's second algorithm (sbm_sampling_axes.hpp;
+//                     project/Ensembles.py:153-157, 200-258)
 //   k_ens_*           statistics over the member axis of an ensemble of trajectories (sbm_ensemble_stats.hpp;
 //                     project/Ensembles.py:277-308, 335-361)
 #include <hip/hip_runtime.h>
@@ -27,6 +30,7 @@
 #include "sbm_plugin.h"
 #include "sbm_sf_quadrature.hpp"
 #include "sbm_ensemble_stats.hpp"
+#include "sbm_sampling_axes.hpp"
 
 // ---------------------------------------------------------------------------
 // errors
@@ -2070,6 +2074,56 @@ extern "C" int sbm_mh_accept(sbm_ctx* ctx, const double* norms_trial, const int3
   SBM_HIP(hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_mh_accept, dim3((C + 3) / 4), dim3(256), 0, ctx->stream, norms_trial, status_trial, entropy_trial, log_u,
                      temperature, C, q, trial, curr, F_curr, n_accepted, ens_slot, ens_F_slot);
+  SBM_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The sampler's second algorithm (project/ensembles.py, sampler='device_recalc'): axes of the candidate density from
+// the Hessian at every chain's point, and the Hastings rule (kernels: sbm_sampling_axes.hpp).
+// ---------------------------------------------------------------------------------------------
+extern "C" int sbm_sampling_axes(sbm_ctx* ctx, const double* J, const double* row_scale, const double* H, int32_t per_chain_H,
+                                 int32_t C, int32_t M, int32_t q, double cutoff, double temperature, double step_scale,
+                                 double* eig, double* V, double* s, double* samp, int32_t* status) {
+  if (!ctx || !status) return sbm_fail(SBM_E_ARG, "sbm_sampling_axes: NULL argument");
+  if ((J == nullptr) == (H == nullptr)) return sbm_fail(SBM_E_ARG, "sbm_sampling_axes: exactly one of J and H must be given");
+  if (H && row_scale) return sbm_fail(SBM_E_ARG, "sbm_sampling_axes: row_scale goes with J");
+  if (C < 0 || q <= 0 || (J && M <= 0)) return sbm_fail(SBM_E_ARG, "sbm_sampling_axes: bad sizes C=%d M=%d q=%d", C, M, q);
+  if (q > SBM_SAMPLING_AXES_MAX_Q)
+    return sbm_fail(SBM_E_ARG, "sbm_sampling_axes: q = %d; two q x (q + 1) matrices are kept in the LDS of one workgroup, which holds "
+                    "SBM_SAMPLING_AXES_MAX_Q = %d", q, SBM_SAMPLING_AXES_MAX_Q);
+  if (!(cutoff >= 0.0) || !(temperature > 0.0) || !(step_scale > 0.0))
+    return sbm_fail(SBM_E_ARG, "sbm_sampling_axes: cutoff must be >= 0, temperature and step_scale positive");
+  if (C == 0) return 0;
+  SBM_HIP(hipSetDevice(ctx->device));
+  const size_t lds = sbm_axes_lds_bytes(q);
+  if (lds > (size_t)lm_lds_limit(ctx))
+    return sbm_fail(SBM_E_ARG, "sbm_sampling_axes: q = %d does not fit the %d KB of LDS of a workgroup", q, lm_lds_limit(ctx) / 1024);
+  sbm_axes_args a{J, row_scale, H, per_chain_H, M, q, cutoff, temperature, step_scale, eig, V, s, samp, status};
+  if (lds > 64 * 1024) SBM_HIP(hipFuncSetAttribute((const void*)k_sampling_axes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_sampling_axes, dim3(C), dim3(256), lds, ctx->stream, a);
+  SBM_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int sbm_mh_accept_hastings(sbm_ctx* ctx, const double* norms_trial, const int32_t* status_trial,
+                                      const double* entropy_trial, const double* log_u, double temperature, int32_t C, int32_t q,
+                                      const double* trial, double* curr, double* F_curr, int32_t* n_accepted, double* ens_slot,
+                                      double* ens_F_slot, double* V_curr, double* s_curr, double* samp_curr, const double* V_trial,
+                                      const double* s_trial, const double* samp_trial, const int32_t* axes_status_trial) {
+  if (!ctx || !norms_trial || !status_trial || !log_u || !trial || !curr || !F_curr || !n_accepted || !V_curr || !s_curr ||
+      !samp_curr || !V_trial || !s_trial || !samp_trial || !axes_status_trial)
+    return sbm_fail(SBM_E_ARG, "sbm_mh_accept_hastings: NULL argument");
+  if (C < 0 || q <= 0) return sbm_fail(SBM_E_ARG, "sbm_mh_accept_hastings: bad sizes C=%d q=%d", C, q);
+  if (!(temperature > 0.0)) return sbm_fail(SBM_E_ARG, "sbm_mh_accept_hastings: temperature must be positive");
+  if (C == 0) return 0;
+  SBM_HIP(hipSetDevice(ctx->device));
+  const size_t lds = sizeof(double) * (size_t)q;
+  if (lds > (size_t)lm_lds_limit(ctx)) return sbm_fail(SBM_E_ARG, "sbm_mh_accept_hastings: q = %d does not fit the LDS of a workgroup", q);
+  sbm_mh_hastings_args a{norms_trial, status_trial, entropy_trial, log_u, temperature, C, q, trial, curr, F_curr, n_accepted,
+                         ens_slot, ens_F_slot, V_curr, s_curr, samp_curr, V_trial, s_trial, samp_trial, axes_status_trial};
+  if (lds > 64 * 1024) SBM_HIP(hipFuncSetAttribute((const void*)k_mh_accept_hastings, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_mh_accept_hastings, dim3(C), dim3(256), lds, ctx->stream, a);
   SBM_HIP(hipGetLastError());
   return 0;
 }

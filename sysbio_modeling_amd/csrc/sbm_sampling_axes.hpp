@@ -1,0 +1,341 @@
+// sbm_sampling_axes.hpp -- kernels of sbm_sampling_axes and sbm_mh_accept_hastings (include/sbm.h): what the second
+// algorithm of the reference's sampler (project/Ensembles.py:153-157, 200-258) needs per chain and step besides the
+// integration -- the eigen-decomposition of the Gauss-Newton Hessian at the trial point with SloppyCell's clipping recipe
+// on top, and the Metropolis-Hastings rule with the candidate density at both ends of the move.
+//
+// k_sampling_axes: one 256-thread workgroup per chain, one launch for everything.
+//   1. A = H / 2.  From a Jacobian: row tiles of J (times row_scale) go through LDS -- the tile borrows the space of V,
+//      which is not needed yet -- and every thread adds the tile's contribution to its entries of A in LDS.  All q^2
+//      entries are formed, not one triangle: fma(x_i, x_j, acc) does not depend on the order of the two factors, so the
+//      two triangles come out equal bit for bit and no mirror pass is needed.  From a matrix: (H + H^T) / 4.
+//   2. Cyclic Jacobi in the round-robin (parallel) ordering: with n = q rounded up to even, a sweep is n - 1 rounds of
+//      n / 2 disjoint pairs (circle method: index n - 1 stays, the others rotate; a pair with the padding index of an odd q
+//      is idle).  In a round thread k computes the rotation of pair k from the current A; then, with barriers between, a
+//      column pass on A, and a row pass on A together with the column pass on V.  A pair is rotated unless
+//      |a_pq| <= DBL_EPSILON sqrt(|a_pp|) sqrt(|a_qq|), and after every sweep all pairs are tested against the same bound
+//      (both on the upper triangle, the one the rotations are computed from; the rotated entry is zeroed on both sides).
+//      The bound is relative to the two diagonal entries, not to ||A||: a sloppy Hessian has eigenvalues many decades
+//      below its largest, and the step lengths are 1 / sqrt of exactly those.  40 sweeps at most.
+//   3. Rank sort of the signed eigenvalues (ascending, as eigh), absolute values, sign convention (the component of
+//      largest magnitude of every eigenvector positive, lowest index on ties), the recipe, the outputs.
+// LDS: A and V at leading dimension q + 1 -- the passes map consecutive lanes to consecutive columns, so the padding only
+// matters to the sign scan down a column -- plus 5 q doubles and 2 q ints: 153 600 bytes at q = SBM_SAMPLING_AXES_MAX_Q = 96.
+// No arrays in registers, no scratch.
+//
+// k_mh_accept_hastings: one workgroup per chain (there are q^2 axis entries to copy on acceptance); the two quadratic
+// forms are strided over the threads and summed in a fixed shape, so every thread takes the same decision.
+#ifndef SBM_SAMPLING_AXES_HPP
+#define SBM_SAMPLING_AXES_HPP
+
+#include <hip/hip_runtime.h>
+#include <float.h>
+#include <stdint.h>
+
+#define SBM_AXES_MAX_SWEEPS 40
+
+struct sbm_axes_args {
+  const double* J;           // [C][M][q] or NULL
+  const double* row_scale;   // [M] or NULL
+  const double* H;           // [q][q] / [C][q][q] or NULL
+  int per_chain_H, M, q;
+  double cutoff, temperature, step_scale;
+  double* eig;               // [C][q]      nullable
+  double* V;                 // [C][q][q]   nullable
+  double* s;                 // [C][q]      nullable
+  double* samp;              // [C][q][q]   nullable
+  int32_t* status;           // [C]
+};
+
+// bytes of dynamic LDS of k_sampling_axes
+static inline size_t sbm_axes_lds_bytes(int q) {
+  const size_t ld = (size_t)q + 1, np = ((size_t)q + 1) / 2;
+  return sizeof(double) * (2 * (size_t)q * ld + 2 * np + 4 * (size_t)q) + sizeof(int) * (2 * np + (size_t)q);
+}
+
+__device__ __forceinline__ double sbm_axes_wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// sum over the 256 threads, the same value on every thread; wavefront partials are added in wavefront order
+__device__ __forceinline__ double sbm_axes_block_sum(double v, double* red /*[4]*/) {
+  v = sbm_axes_wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__device__ __forceinline__ bool sbm_axes_finite(double x) { return fabs(x) <= DBL_MAX; }      // (false for NaN)
+
+__global__ void __launch_bounds__(256) k_sampling_axes(sbm_axes_args a) {
+  extern __shared__ __attribute__((aligned(16))) double ax_smem[];
+  const int c = blockIdx.x, tid = threadIdx.x, q = a.q, ld = q + 1;
+  const int ne = (q + 1) & ~1, np = ne / 2, nr = ne - 1;      // players, pairs of a round, rounds of a sweep
+  double* A = ax_smem;                         // [q][ld]
+  double* Vm = A + (size_t)q * ld;             // [q][ld]  eigenvectors in the columns; before that the row tile of J
+  double* rc = Vm + (size_t)q * ld;            // [np]     cosines of the round
+  double* rs = rc + np;                        // [np]     sines
+  double* ev = rs + np;                        // [q]      signed eigenvalues, by column of Vm
+  double* av = ev + q;                         // [q]      |eigenvalue|, sorted
+  double* sv = av + q;                         // [q]      step lengths, sorted
+  double* sg = sv + q;                         // [q]      sign of the eigenvector, by column of Vm
+  int* pp = (int*)(sg + q);                    // [np]     first index of the pair
+  int* pq = pp + np;                           // [np]     second index (> first), -1: nothing to do
+  int* perm = pq + np;                         // [q]      column of Vm that holds the k-th eigenvalue
+  const int qq = q * q;
+  int bad = 0;
+
+  // ---- 1. A = H / 2
+  if (a.J) {
+    const int M = a.M, TILE = q < 32 ? q : 32;
+    const double* Jc = a.J + (size_t)c * M * q;
+    double* T = Vm;
+    for (int e = tid; e < qq; e += 256) A[(e / q) * ld + e % q] = 0.0;
+    for (int m0 = 0; m0 < M; m0 += TILE) {
+      const int rows = min(TILE, M - m0);
+      __syncthreads();
+      for (int e = tid; e < rows * q; e += 256) {
+        const int rr = e / q, cc = e - rr * q;
+        double val = Jc[(size_t)(m0 + rr) * q + cc];
+        if (a.row_scale) val *= a.row_scale[m0 + rr];
+        T[rr * ld + cc] = val;
+        bad |= !sbm_axes_finite(val);
+      }
+      __syncthreads();
+      for (int e = tid; e < qq; e += 256) {
+        const int i = e / q, j = e - i * q;
+        double acc = A[i * ld + j];
+        for (int rr = 0; rr < rows; ++rr) acc = fma(T[rr * ld + i], T[rr * ld + j], acc);
+        A[i * ld + j] = acc;
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < qq; e += 256) {
+      const int i = e / q, j = e - i * q;
+      const double v = 0.5 * A[i * ld + j];
+      A[i * ld + j] = v;
+      bad |= !sbm_axes_finite(v);
+    }
+  } else {
+    const double* Hc = a.H + (a.per_chain_H ? (size_t)c * qq : 0);
+    for (int e = tid; e < qq; e += 256) {
+      const int i = e / q, j = e - i * q;
+      const double hij = Hc[(size_t)i * q + j], hji = Hc[(size_t)j * q + i];
+      const double v = 0.5 * (0.5 * hij + 0.5 * hji);
+      A[i * ld + j] = v;
+      bad |= !sbm_axes_finite(hij) || !sbm_axes_finite(v);
+    }
+  }
+  for (int e = tid; e < qq; e += 256) {
+    const int i = e / q, j = e - i * q;
+    Vm[i * ld + j] = i == j ? 1.0 : 0.0;
+  }
+  bad = __syncthreads_or(bad);
+
+  // ---- 2. Jacobi
+  int sweeps = 0;
+  bool converged = false;
+  while (!bad) {
+    int open = 0;
+    for (int e = tid; e < qq; e += 256) {
+      const int i = e / q, j = e - i * q;
+      if (i < j) open |= !(fabs(A[i * ld + j]) <= DBL_EPSILON * sqrt(fabs(A[i * ld + i])) * sqrt(fabs(A[j * ld + j])));
+    }
+    if (!__syncthreads_or(open)) { converged = true; break; }
+    if (sweeps == SBM_AXES_MAX_SWEEPS) break;
+    for (int r = 0; r < nr; ++r) {
+      if (tid < np) {
+        int p = tid == 0 ? nr : (r + tid) % nr;
+        int s2 = tid == 0 ? r : (r - tid + nr) % nr;
+        if (p > s2) { const int t = p; p = s2; s2 = t; }
+        double cs = 1.0, sn = 0.0;
+        int second = -1;
+        if (s2 < q) {
+          const double apq = A[p * ld + s2], app = A[p * ld + p], aqq = A[s2 * ld + s2];
+          if (!(fabs(apq) <= DBL_EPSILON * sqrt(fabs(app)) * sqrt(fabs(aqq)))) {
+            const double theta = (aqq - app) / (2.0 * apq);
+            // the smaller root of t^2 + 2 theta t - 1 = 0; theta beyond the range of its square: t = 1 / (2 theta)
+            const double t = fabs(theta) > 1.0e150 ? 0.5 / theta
+                                                   : copysign(1.0, theta) / (fabs(theta) + sqrt(fma(theta, theta, 1.0)));
+            cs = 1.0 / sqrt(fma(t, t, 1.0));
+            sn = t * cs;
+            second = s2;
+          }
+        }
+        pp[tid] = p;
+        pq[tid] = second;
+        rc[tid] = cs;
+        rs[tid] = sn;
+      }
+      __syncthreads();
+      // A <- A P: columns p and s2 of every row (consecutive lanes: consecutive pairs, i.e. consecutive columns)
+      for (int e = tid; e < np * q; e += 256) {
+        const int i = e / np, k = e - i * np;
+        const int s2 = pq[k];
+        if (s2 < 0) continue;
+        const int p = pp[k];
+        const double cs = rc[k], sn = rs[k];
+        const double x = A[i * ld + p], y = A[i * ld + s2];
+        A[i * ld + p] = fma(cs, x, -sn * y);
+        A[i * ld + s2] = fma(sn, x, cs * y);
+      }
+      __syncthreads();
+      // A <- P^T A: rows p and s2, the rotated entry set to zero on both sides; V <- V P
+      for (int e = tid; e < 2 * np * q; e += 256) {
+        const bool on_v = e >= np * q;
+        const int f = on_v ? e - np * q : e;
+        if (!on_v) {
+          const int k = f / q, j = f - k * q;
+          const int s2 = pq[k];
+          if (s2 < 0) continue;
+          const int p = pp[k];
+          const double cs = rc[k], sn = rs[k];
+          const double x = A[p * ld + j], y = A[s2 * ld + j];
+          A[p * ld + j] = j == s2 ? 0.0 : fma(cs, x, -sn * y);
+          A[s2 * ld + j] = j == p ? 0.0 : fma(sn, x, cs * y);
+        } else {
+          const int i = f / np, k = f - i * np;
+          const int s2 = pq[k];
+          if (s2 < 0) continue;
+          const int p = pp[k];
+          const double cs = rc[k], sn = rs[k];
+          const double x = Vm[i * ld + p], y = Vm[i * ld + s2];
+          Vm[i * ld + p] = fma(cs, x, -sn * y);
+          Vm[i * ld + s2] = fma(sn, x, cs * y);
+        }
+      }
+      __syncthreads();
+    }
+    ++sweeps;
+  }
+
+  if (!converged) {
+    const double nan = __builtin_nan("");
+    for (int e = tid; e < qq; e += 256) {
+      if (a.V) a.V[(size_t)c * qq + e] = 0.0;
+      if (a.samp) a.samp[(size_t)c * qq + e] = 0.0;
+    }
+    for (int i = tid; i < q; i += 256) {
+      if (a.eig) a.eig[(size_t)c * q + i] = nan;
+      if (a.s) a.s[(size_t)c * q + i] = nan;
+    }
+    if (tid == 0) a.status[c] = 1;
+    return;
+  }
+
+  // ---- 3. order, signs, recipe
+  for (int i = tid; i < q; i += 256) ev[i] = A[i * ld + i];
+  __syncthreads();
+  for (int i = tid; i < q; i += 256) {
+    const double d = ev[i];
+    int rank = 0;
+    for (int j = 0; j < q; ++j) rank += (ev[j] < d) || (ev[j] == d && j < i);
+    perm[rank] = i;
+    av[rank] = fabs(d);
+    double best = 0.0, val = 1.0;
+    for (int r = 0; r < q; ++r) {
+      const double x = Vm[r * ld + i];
+      if (fabs(x) > best) { best = fabs(x); val = x; }
+    }
+    sg[i] = val < 0.0 ? -1.0 : 1.0;
+  }
+  __syncthreads();
+  for (int k = tid; k < q; k += 256) {
+    double amax = 0.0;
+    for (int j = 0; j < q; ++j) amax = fmax(amax, av[j]);
+    const double cut = a.cutoff * amax;
+    double n_eff = (double)q;
+    if (cut > 0.0) {
+      n_eff = 0.0;
+      for (int j = 0; j < q; ++j) n_eff += fmin(av[j] / cut, 1.0);
+    }
+    sv[k] = a.step_scale * sqrt(a.temperature / n_eff) / sqrt(fmax(av[k], fmax(cut, DBL_MIN)));
+    if (a.eig) a.eig[(size_t)c * q + k] = av[k];
+    if (a.s) a.s[(size_t)c * q + k] = sv[k];
+  }
+  __syncthreads();
+  for (int e = tid; e < qq; e += 256) {
+    const int r = e / q, k = e - r * q;
+    const int col = perm[k];
+    const double v = sg[col] * Vm[r * ld + col];
+    if (a.V) a.V[(size_t)c * qq + e] = v;
+    if (a.samp) a.samp[(size_t)c * qq + e] = v * sv[k];
+  }
+#ifdef SBM_AXES_STATUS_CARRIES_SWEEPS
+  if (tid == 0) a.status[c] = sweeps << 8;      // developer builds only: the sweep count for the measurements of docs/history.md
+#else
+  if (tid == 0) a.status[c] = 0;
+#endif
+}
+
+struct sbm_mh_hastings_args {
+  const double* norms_t;       // [C]
+  const int32_t* status_t;     // [C]
+  const double* entropy_t;     // [C] nullable
+  const double* log_u;         // [C]
+  double temperature;
+  int C, q;
+  const double* trial;         // [C][q]
+  double* curr;                // [C][q]    in / out
+  double* F_curr;              // [C]       in / out
+  int32_t* n_accepted;         // [C]       in / out
+  double* ens_slot;            // [C][q]    nullable
+  double* ens_F_slot;          // [C]       nullable
+  double *V_curr, *s_curr, *samp_curr;                     // [C][q][q], [C][q], [C][q][q]   in / out
+  const double *V_trial, *s_trial, *samp_trial;
+  const int32_t* axes_status_t;                            // [C]
+};
+
+__global__ void __launch_bounds__(256) k_mh_accept_hastings(sbm_mh_hastings_args a) {
+  extern __shared__ __attribute__((aligned(16))) double hs_d[];      // [q] the move
+  __shared__ double s_red[4];
+  const int c = blockIdx.x, tid = threadIdx.x, q = a.q;
+  const size_t o1 = (size_t)c * q, o2 = o1 * q;
+  for (int i = tid; i < q; i += 256) hs_d[i] = a.trial[o1 + i] - a.curr[o1 + i];
+  __syncthreads();
+  // log q(d; V, s) = -0.5 |V^T d / s|^2 - sum log s: forward with the current axes, back (-d) with the trial point's
+  double fwd = 0.0, back = 0.0;
+  for (int i = tid; i < q; i += 256) {
+    double uc = 0.0, ut = 0.0;
+    for (int j = 0; j < q; ++j) {
+      uc = fma(a.V_curr[o2 + (size_t)j * q + i], hs_d[j], uc);
+      ut = fma(a.V_trial[o2 + (size_t)j * q + i], -hs_d[j], ut);
+    }
+    const double sc = a.s_curr[o1 + i], st = a.s_trial[o1 + i];
+    uc /= sc;
+    ut /= st;
+    fwd += -0.5 * uc * uc - log(sc);
+    back += -0.5 * ut * ut - log(st);
+  }
+  fwd = sbm_axes_block_sum(fwd, s_red);
+  back = sbm_axes_block_sum(back, s_red);
+  const double Fc = a.F_curr[c];
+  const double Ft = 0.5 * a.norms_t[c] - (a.entropy_t ? a.entropy_t[c] : 0.0);
+  const bool acc = a.status_t[c] == 0 && a.axes_status_t[c] == 0 && sbm_axes_finite(Ft) &&
+                   a.log_u[c] < -(Ft - Fc) / a.temperature + back - fwd;
+  __syncthreads();                // every thread has read F_curr and the current axes
+  for (int i = tid; i < q; i += 256) {
+    const double x = acc ? a.trial[o1 + i] : a.curr[o1 + i];
+    if (acc) {
+      a.curr[o1 + i] = x;
+      a.s_curr[o1 + i] = a.s_trial[o1 + i];
+    }
+    if (a.ens_slot) a.ens_slot[o1 + i] = x;
+  }
+  if (acc)
+    for (int e = tid; e < q * q; e += 256) {
+      a.V_curr[o2 + e] = a.V_trial[o2 + e];
+      a.samp_curr[o2 + e] = a.samp_trial[o2 + e];
+    }
+  if (tid == 0) {
+    if (acc) {
+      a.F_curr[c] = Ft;
+      a.n_accepted[c] += 1;
+    }
+    if (a.ens_F_slot) a.ens_F_slot[c] = acc ? Ft : Fc;
+  }
+}
+
+#endif  // SBM_SAMPLING_AXES_HPP

@@ -1,7 +1,7 @@
 from .base_project import Project
 from . import utils
-from .ensembles import (EnsembleTrajectories, ensemble_predictions, ensemble_trajs, net_ensemble_trajs,
-                        traj_ensemble_quantiles, traj_ensemble_stats)
+from .ensembles import (EnsembleTrajectories, ensemble_predictions, ensemble_trajs, net_ensemble_trajs, pca_eig,
+                        pca_eig_log_params, traj_ensemble_quantiles, traj_ensemble_stats)
 
 __all__ = ['Project', 'utils', 'EnsembleTrajectories', 'ensemble_predictions', 'ensemble_trajs', 'net_ensemble_trajs',
-           'traj_ensemble_quantiles', 'traj_ensemble_stats']
+           'pca_eig', 'pca_eig_log_params', 'traj_ensemble_quantiles', 'traj_ensemble_stats']

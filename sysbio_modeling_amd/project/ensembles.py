@@ -93,25 +93,46 @@ def ensemble_log_params_batch(project, params, hess=None, steps=1000, temperatur
              Same candidate density, same acceptance rule, same return shapes; another random stream, and the entropy
              by a fixed-node rule instead of ``scipy.integrate.quad``.  ``method='auto'`` / ``'implicit_controlled'``
              are host control loops: the integration then goes through ``evaluate_batch`` and the rest stays on the
-             device.  ``recalc_hess_alg=True`` needs an eigen-decomposition per chain and step, which stays on the host
-             path: with ``sampler='device'`` it raises ValueError.
+             device.  ``sampler='device'`` is the first algorithm only: with ``recalc_hess_alg=True`` it raises ValueError
+             and points at 'device_recalc'.
+             'device_recalc': the second algorithm (``recalc_hess_alg`` is implied and ignored) with the whole step on
+             the device -- ``sbm_mh_propose`` with one matrix per chain, ``sbm_jacobian_batch``, ``sbm_project_sf_entropy``,
+             ``sbm_sampling_axes`` (the Gauss-Newton Hessian of every trial point, its eigen-decomposition and the
+             clipping recipe in one launch), ``sbm_mh_accept_hastings`` -- no read-back, one synchronisation at the end.
+             The first axes come from ``hess`` when given (the same for all chains), else from the Jacobian at the
+             starts.  A trial point whose Jacobian is not finite is rejected.  At most ``_lib.SAMPLING_AXES_MAX_Q`` = 96
+             parameters.
     draws : (z, log_u) of shapes (steps, C, q) and (steps, C): the standard normal and log-uniform numbers to use
-             instead of drawing them (``sampler='device'`` only).
+             instead of drawing them (the two device samplers only).  With 'device_recalc' the move is V (s z) with the
+             eigenvectors signed as ``sbm_sampling_axes`` signs them (include/sbm.h).
     Returns (ens, ens_Fs, ratio): ens (n_kept, C, q) parameter sets including the starts, ens_Fs
     (n_kept, C) their energies, ratio (C,) accepted / attempted per chain.
     """
     starts = np.atleast_2d(np.asarray(params, dtype=float))
     C, q = starts.shape
-    if sampler not in ('host', 'device'):
-        raise ValueError("sampler must be 'host' or 'device', not %r" % (sampler,))
+    if sampler not in ('host', 'device', 'device_recalc'):
+        raise ValueError("sampler must be 'host', 'device' or 'device_recalc', not %r" % (sampler,))
     if sampler == 'device' and recalc_hess_alg:
-        raise ValueError("recalc_hess_alg=True takes an eigen-decomposition per chain and step on the host: use sampler='host'")
-    if draws is not None and sampler != 'device':
-        raise ValueError("draws= is an argument of sampler='device'")
+        raise ValueError("sampler='device' is the first algorithm (one Hessian for the whole run): for recalc_hess_alg=True "
+                         "use sampler='device_recalc' (or sampler='host')")
+    if draws is not None and sampler == 'host':
+        raise ValueError("draws= is an argument of sampler='device' and sampler='device_recalc'")
+    if sampler == 'device_recalc':
+        from .. import _lib
+        if q > _lib.SAMPLING_AXES_MAX_Q:
+            raise ValueError("sampler='device_recalc': %d parameters; sbm_sampling_axes keeps the Hessian and its eigenvectors in "
+                             "the LDS of one workgroup, which holds q <= %d (use sampler='host')" % (q, _lib.SAMPLING_AXES_MAX_Q))
     sfs = list(project.scale_factors.values()) if project.scale_factors is not None else []
     if energy == 'auto':
         energy = 'free_energy' if sfs and all(sf.log_prior is not None for sf in sfs) else 'rss'
 
+    if sampler == 'device_recalc':
+        recalc = dict(hess=None if hess is None else np.ascontiguousarray(hess, dtype=np.float64), cutoff=float(sing_val_cutoff),
+                      step_scale=float(step_scale))
+        if recalc['hess'] is not None and recalc['hess'].shape != (q, q):
+            raise ValueError("hess must have shape (%d, %d), not %s" % (q, q, recalc['hess'].shape))
+        return _device_chains(project, starts, None, int(steps), float(temperature), seeds, int(skip_elems), energy, draws,
+                              integrator_overrides, recalc=recalc)
     if sampler == 'device':
         if hess is None:
             hess = _gauss_newton_hessians(project, starts[:1], _inv_sigma(project), integrator_overrides)[0]
@@ -170,10 +191,15 @@ def ensemble_log_params_batch(project, params, hess=None, steps=1000, temperatur
 _DRAW_BLOCK = 256      # steps whose random numbers are drawn at once
 
 
-def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems, energy, draws, overrides):
+def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems, energy, draws, overrides, recalc=None):
     """The loop of ``ensemble_log_params_batch(sampler='device')``: per step four enqueues on the context's stream and
     no read-back; the record is a preallocated device array that ``sbm_mh_accept`` writes every (skip_elems + 1)-th
-    step."""
+    step.
+
+    With ``recalc`` = dict(hess, cutoff, step_scale) the loop of ``sampler='device_recalc'``: ``samp`` is not used, every
+    chain keeps the axes (V, s, samp = V diag(s)) of its current point; per step five enqueues -- the evaluation is
+    ``sbm_jacobian_batch``, ``sbm_sampling_axes`` turns the trial points' Jacobians into their axes, and
+    ``sbm_mh_accept_hastings`` decides with the candidate density at both ends and moves the axes with the point."""
     import ctypes
     import torch
     from .. import _control, _lib
@@ -193,7 +219,19 @@ def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems,
     G = project._n_sf_groups()
     curr = torch.from_numpy(np.ascontiguousarray(starts)).to(dev)
     trial = torch.empty_like(curr)
-    samp_d = torch.from_numpy(np.ascontiguousarray(samp, dtype=np.float64)).to(dev)
+    if recalc is None:
+        samp_d = torch.from_numpy(np.ascontiguousarray(samp, dtype=np.float64)).to(dev)
+    else:
+        jac = torch.empty((C, RT, q), dtype=f64, device=dev)
+        # axes of the current points and of the trial points: V, s, samp
+        ax_c = [torch.empty(sh, dtype=f64, device=dev) for sh in ((C, q, q), (C, q), (C, q, q))]
+        ax_t = [torch.empty(sh, dtype=f64, device=dev) for sh in ((C, q, q), (C, q), (C, q, q))]
+        ax_status = torch.empty((C,), dtype=i32, device=dev)
+        row_scale = None
+        inv_sigma = _inv_sigma(project)
+        if inv_sigma is not None:       # the measurement rows of a reference_compat Jacobian come undivided by sigma
+            row_scale = torch.ones((RT,), dtype=f64, device=dev)
+            row_scale[:R] = torch.from_numpy(np.ascontiguousarray(inv_sigma, dtype=np.float64)).to(dev)
     sims = torch.empty((C, R), dtype=f64, device=dev)
     resid = torch.empty((C, RT), dtype=f64, device=dev)
     sf = torch.empty((C, G), dtype=f64, device=dev) if G else None
@@ -205,10 +243,18 @@ def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems,
     opts = None if host_loop else project._opts(**overrides)
 
     def evaluate(th):
-        """norms, status (and sims) of the C points ``th``; entropy of their simulations"""
+        """norms, status (and sims) of the C points ``th``; entropy of their simulations; with ``recalc`` their Jacobians"""
         if host_loop:
-            res = project.evaluate_batch(th, want=('sims', 'norms', 'status'), **overrides)
+            if recalc is not None:
+                res = project.evaluate_batch(th, jacobian=True, want=('sims', 'norms', 'status', 'jacobian'), **overrides)
+                jac.copy_(res['jacobian'])
+            else:
+                res = project.evaluate_batch(th, want=('sims', 'norms', 'status'), **overrides)
             nr, st, sm = res['norms'].contiguous(), res['status'].to(i32).contiguous(), res['sims'].contiguous()
+        elif recalc is not None:
+            _lib.check(lib.sbm_jacobian_batch(proj, p(th), C, ctypes.byref(opts), p(sims), p(resid), p(jac), None, p(sf), None,
+                                              p(norms), None, p(status), p(n_steps)), 'sbm_jacobian_batch')
+            nr, st, sm = norms, status, sims
         else:
             _lib.check(lib.sbm_residuals_batch(proj, p(th), C, ctypes.byref(opts), p(sims), p(resid), p(sf), p(norms),
                                                p(status), p(n_steps)), 'sbm_residuals_batch')
@@ -217,7 +263,16 @@ def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems,
             _lib.check(lib.sbm_project_sf_entropy(proj, p(sm), C, temperature, p(entropy), None), 'sbm_project_sf_entropy')
         return nr, st
 
+    def axes(out, hess=None):
+        """V, s, samp of the points whose Jacobians ``evaluate`` left in ``jac`` (or of one Hessian for all chains)"""
+        H = None if hess is None else torch.from_numpy(hess).to(dev)
+        _lib.check(lib.sbm_sampling_axes(ctx.handle, p(jac) if H is None else None, p(row_scale) if H is None else None, p(H), 0,
+                                         C, RT, q, recalc['cutoff'], temperature, recalc['step_scale'], None, p(out[0]),
+                                         p(out[1]), p(out[2]), p(ax_status)), 'sbm_sampling_axes')
+
     nr, st = evaluate(curr)
+    if recalc is not None:
+        axes(ax_c, recalc['hess'])
     F = 0.5 * nr - entropy if free else 0.5 * nr
     F_curr = torch.where(torch.isfinite(F) & (st == 0), F, torch.full_like(F, float('inf'))).contiguous()
     every = skip_elems + 1
@@ -250,15 +305,70 @@ def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems,
                 z_blk = torch.randn((n, C, q), dtype=f64, device=dev, generator=gen)
                 u_blk = torch.log(torch.rand((n, C), dtype=f64, device=dev, generator=gen))
             z, log_u = z_blk[k], u_blk[k]
-        _lib.check(lib.sbm_mh_propose(ctx.handle, p(curr), p(samp_d), 0, p(z), C, q, p(trial)), 'sbm_mh_propose')
+        if recalc is None:
+            _lib.check(lib.sbm_mh_propose(ctx.handle, p(curr), p(samp_d), 0, p(z), C, q, p(trial)), 'sbm_mh_propose')
+        else:
+            _lib.check(lib.sbm_mh_propose(ctx.handle, p(curr), p(ax_c[2]), 1, p(z), C, q, p(trial)), 'sbm_mh_propose')
         nr, st = evaluate(trial)
         slot = step // every if step % every == 0 else None
+        if recalc is not None:
+            axes(ax_t)
+            _lib.check(lib.sbm_mh_accept_hastings(ctx.handle, p(nr), p(st), p(entropy), p(log_u), temperature, C, q, p(trial), p(curr),
+                                                  p(F_curr), p(n_acc), p(ens[slot]) if slot is not None else None,
+                                                  p(ens_F[slot]) if slot is not None else None, p(ax_c[0]), p(ax_c[1]), p(ax_c[2]),
+                                                  p(ax_t[0]), p(ax_t[1]), p(ax_t[2]), p(ax_status)), 'sbm_mh_accept_hastings')
+            continue
         _lib.check(lib.sbm_mh_accept(ctx.handle, p(nr), p(st), p(entropy), p(log_u), temperature, C, q, p(trial), p(curr),
                                      p(F_curr), p(n_acc), p(ens[slot]) if slot is not None else None,
                                      p(ens_F[slot]) if slot is not None else None), 'sbm_mh_accept')
     ctx.synchronize()
     torch.cuda.synchronize(dev)
     return ens.cpu().numpy(), ens_F.cpu().numpy(), n_acc.cpu().numpy() / max(steps, 1)
+
+
+# ---------------------------------------------------------------------------------------------
+# Principal components of an ensemble (reference project/Ensembles.py:363-382)
+# ---------------------------------------------------------------------------------------------
+def pca_eig(ens):
+    """Principal component analysis of an ensemble (reference PCA_eig): (values (q,), vectors (q, q)), scaled and ordered
+    so that they can be set beside the eigen-system of J^T J -- values n / sigma_i^2 with sigma_i the singular values of
+    the centred (n, q) ensemble, largest value (tightest direction) first, the vectors in the columns.  ``ens`` is
+    (n, q) or the sampler's (n_kept, C, q), which is flattened; it is not modified (the reference centres in place and
+    adds the mean back).  One ``sbm_sampling_axes`` call on the centred ensemble as the 'Jacobian' of a single chain:
+    the eigenvalues a of X^T X / 2, ascending, are sigma^2 / 2, so the values are n / (2 a) and the vectors come signed
+    by that entry's convention.  q <= 96."""
+    import torch
+    from .. import _lib
+    X = np.array(ens, dtype=np.float64)
+    if X.ndim == 3:
+        X = X.reshape(-1, X.shape[-1])
+    if X.ndim != 2 or X.shape[0] == 0:
+        raise ValueError("ensemble must have shape (n, q) or (n_kept, C, q), not %s" % (np.shape(ens),))
+    n, q = X.shape
+    if q > _lib.SAMPLING_AXES_MAX_Q:
+        raise ValueError("pca_eig: %d parameters; sbm_sampling_axes holds q <= %d" % (q, _lib.SAMPLING_AXES_MAX_Q))
+    X -= X.mean(axis=0)
+    lib = _lib.load_library()
+    ctx = _lib.default_context()
+    dev = torch.device('cuda', ctx.device)
+    Xd = torch.from_numpy(np.ascontiguousarray(X)).to(dev)
+    eig = torch.empty((q,), dtype=torch.float64, device=dev)
+    V = torch.empty((q, q), dtype=torch.float64, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    p = _lib.dev_ptr
+    _lib.check(lib.sbm_sampling_axes(ctx.handle, p(Xd), None, None, 0, 1, n, q, 0.0, 1.0, 1.0, p(eig), p(V), None, None,
+                                     p(status)), 'sbm_sampling_axes')
+    ctx.synchronize()
+    torch.cuda.synchronize(dev)
+    if int(status.item()) != 0:
+        raise ValueError("pca_eig: the ensemble has entries that are not finite")
+    with np.errstate(divide='ignore'):
+        return n / (2.0 * eig.cpu().numpy()), V.cpu().numpy()
+
+
+def pca_eig_log_params(ens):
+    """``pca_eig`` of the logarithms of an ensemble of (positive) parameters (reference PCA_eig_log_params)."""
+    return pca_eig(np.log(np.asarray(ens, dtype=np.float64)))
 
 
 # ---------------------------------------------------------------------------------------------
