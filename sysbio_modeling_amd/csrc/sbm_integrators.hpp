@@ -332,6 +332,17 @@ __device__ __forceinline__ void sbm_report(const sbm_kernel_args& a, int traj, i
   }
 }
 
+// Whether sbm_dopri45 folds the step size into the tableau (products hs * a_ij formed per stage, see there): yes,
+// except in the per-wave SensSystem of a model whose seven stage vectors do not fit the register file of a wave
+// (7 vectors x 2 VGPRs x more than 36 elements per lane > 512; stiff50 has 50).  That kernel keeps its stage
+// vectors in scratch as it is, and the compiler's report has MORE scratch instructions in its step loop with the
+// products alive (1068) than without (1038), so it keeps the form that scales each finished sum.  The state and
+// row-lane kernels of the same model go the other way (1362 -> 1262, 706 -> 543) and fold.
+template <class Sys>
+inline constexpr bool sbm_fold_step_size = true;
+template <class M>
+inline constexpr bool sbm_fold_step_size<SensSystem<M>> = (SensSystem<M>::CPL * M::NV <= 36);
+
 // Dormand-Prince 5(4) with FSAL, I-controller (safety 0.9, factor in [0.2, 10]),
 // landing exactly on every output time (the reference samples the solution AT
 // grid points, project/utils.py:18-21 -- no dense output, no interpolation).
@@ -424,44 +435,79 @@ __device__ __forceinline__ SbmTrajOut sbm_dopri45(const Sys& sys, double (&z)[Sy
       bool last = false;
       if (t + 1.01 * hs >= target) { hs = target - t; last = true; }
 
-      // The tableau entries stay compile-time constants (SGPR literals the compiler can rematerialise at
-      // will) and the step size multiplies each finished sum once: the 26 products h*a_ij, h*e_j would
-      // otherwise sit in 52 VGPRs for the whole step -- a fifth of the register budget of a wave that
-      // needs every register for its stage vectors (there is no scalar fp64 ALU to keep them in SGPRs).
-      // Price: one more FMA per element in stages 3-7.
+      // The step size is folded into the tableau: stage s is formed from the products hs * a_sj as one FMA chain
+      // seeded with z, so no sum is opened by a multiply and none is scaled afterwards -- one VALU instruction
+      // less per element in each of stages 3-7.  The products are formed from the CLIPPED step size hs, once per
+      // attempted step (a rejection comes back through here with its new hs), and each right before the stage
+      // that reads it first, NOT at the top of the step: there is no scalar fp64 ALU, so a product is a VGPR pair
+      // for as long as it lives, and all 19 of them held for the whole step would be 38 VGPRs of a wave that
+      // needs every register for its stage vectors.  Formed per stage they are transient: at most 11 are alive
+      // at once (the three chains of stage 5: 22 VGPRs, where 6 of the 7 stage vectors are alive), 2-3 elsewhere.
+      // They are wave-uniform: 19 v_mul_f64 per step against 5 instructions per ELEMENT saved.  The tableau
+      // entries themselves stay compile-time constants (SGPR literals the compiler can rematerialise at will).
       //
       // Stages 2-4 combine the stored derivatives.  From stage 5 on every remaining linear
       // combination (the inputs of stages 6 and 7 and the error estimate) is carried as a RUNNING SUM
       // instead: when the input of stage 5 is formed, k2 / k3 / k4 are read one last time and their
-      // registers take over the partial sums U6 / U7 / E (unscaled by h).  Each derivative is read
-      // once instead of up to four times and the live set peaks at 7 stage vectors instead of 8
-      // (z, k1, zt, U6, U7, E, k5), falling to 5 by stage 7 -- it is the v_accvgpr traffic of an
+      // registers take over U6 / U7 (the arguments of stages 6 and 7 short of their last term: z plus the
+      // scaled terms known so far) and E (the error sum, unscaled by h: |hs| multiplies its norm once).
+      // Each derivative is read once instead of up to four times and the live set peaks at 7 stage vectors
+      // instead of 8 (z, k1, zt, U6, U7, E, k5), falling to 5 by stage 7 -- it is the v_accvgpr traffic of an
       // overflowing register file that this saves.
+      //
+      // kFold == false (the per-wave system of a large model, see sbm_fold_step_size) keeps the
+      // earlier form: tableau literals inside the sums, each finished sum scaled by hs with one more FMA.
+      constexpr bool kFold = sbm_fold_step_size<Sys>;
       const double ha21 = hs * A21;
+      double ha31, ha32, ha41, ha42, ha43, ha51, ha52, ha53, ha54, ha61, ha62, ha63, ha64, ha71, ha73, ha74, ha65, ha75,
+          ha76;
 #define SBM_S2 zt[c][i] = fma(ha21, k1[c][i], z[c][i]);
-#define SBM_S3 zt[c][i] = fma(hs, fma(A32, k2[c][i], A31 * k1[c][i]), z[c][i]);
-#define SBM_S4 zt[c][i] = fma(hs, fma(A43, k3[c][i], fma(A42, k2[c][i], A41 * k1[c][i])), z[c][i]);
-#define SBM_S5                                                                    \
-  const double a1_ = k1[c][i], a2_ = k2[c][i], a3_ = k3[c][i], a4_ = k4[c][i];    \
-  zt[c][i] = fma(hs, fma(A54, a4_, fma(A53, a3_, fma(A52, a2_, A51 * a1_))), z[c][i]); \
-  k2[c][i] = fma(A64, a4_, fma(A63, a3_, fma(A62, a2_, A61 * a1_))); /* U6 */     \
-  k3[c][i] = fma(A74, a4_, fma(A73, a3_, A71 * a1_));                /* U7 */     \
-  k4[c][i] = fma(E4, a4_, fma(E3, a3_, E1 * a1_));                   /* E  */
-#define SBM_S6                                              \
-  const double a5_ = k5[c][i];                              \
-  zt[c][i] = fma(hs, fma(A65, a5_, k2[c][i]), z[c][i]);     \
-  k3[c][i] = fma(A75, a5_, k3[c][i]);                       \
+#define SBM_S3                                                                                    \
+  if constexpr (kFold) zt[c][i] = fma(ha32, k2[c][i], fma(ha31, k1[c][i], z[c][i]));              \
+  else zt[c][i] = fma(hs, fma(A32, k2[c][i], A31 * k1[c][i]), z[c][i]);
+#define SBM_S4                                                                                               \
+  if constexpr (kFold) zt[c][i] = fma(ha43, k3[c][i], fma(ha42, k2[c][i], fma(ha41, k1[c][i], z[c][i])));    \
+  else zt[c][i] = fma(hs, fma(A43, k3[c][i], fma(A42, k2[c][i], A41 * k1[c][i])), z[c][i]);
+#define SBM_S5                                                                                    \
+  const double a1_ = k1[c][i], a2_ = k2[c][i], a3_ = k3[c][i], a4_ = k4[c][i], z_ = z[c][i];      \
+  if constexpr (kFold) {                                                                          \
+    zt[c][i] = fma(ha54, a4_, fma(ha53, a3_, fma(ha52, a2_, fma(ha51, a1_, z_))));                \
+    k2[c][i] = fma(ha64, a4_, fma(ha63, a3_, fma(ha62, a2_, fma(ha61, a1_, z_)))); /* U6 */       \
+    k3[c][i] = fma(ha74, a4_, fma(ha73, a3_, fma(ha71, a1_, z_)));                 /* U7 */       \
+  } else {                                                                                        \
+    zt[c][i] = fma(hs, fma(A54, a4_, fma(A53, a3_, fma(A52, a2_, A51 * a1_))), z_);               \
+    k2[c][i] = fma(A64, a4_, fma(A63, a3_, fma(A62, a2_, A61 * a1_)));                            \
+    k3[c][i] = fma(A74, a4_, fma(A73, a3_, A71 * a1_));                                           \
+  }                                                                                               \
+  k4[c][i] = fma(E4, a4_, fma(E3, a3_, E1 * a1_));                                 /* E  */
+#define SBM_S6                                                        \
+  const double a5_ = k5[c][i];                                        \
+  if constexpr (kFold) zt[c][i] = fma(ha65, a5_, k2[c][i]);           \
+  else zt[c][i] = fma(hs, fma(A65, a5_, k2[c][i]), z[c][i]);          \
+  if constexpr (kFold) k3[c][i] = fma(ha75, a5_, k3[c][i]);           \
+  else k3[c][i] = fma(A75, a5_, k3[c][i]);                            \
   k4[c][i] = fma(E5, a5_, k4[c][i]);
-#define SBM_S7                                              \
-  const double a6_ = k6[c][i];                              \
-  zt[c][i] = fma(hs, fma(A76, a6_, k3[c][i]), z[c][i]);     \
+#define SBM_S7                                                        \
+  const double a6_ = k6[c][i];                                        \
+  if constexpr (kFold) zt[c][i] = fma(ha76, a6_, k3[c][i]);           \
+  else zt[c][i] = fma(hs, fma(A76, a6_, k3[c][i]), z[c][i]);          \
   k4[c][i] = fma(E6, a6_, k4[c][i]);
+#define SBM_P3 if constexpr (kFold) { ha31 = hs * A31; ha32 = hs * A32; }
+#define SBM_P4 if constexpr (kFold) { ha41 = hs * A41; ha42 = hs * A42; ha43 = hs * A43; }
+#define SBM_P5                                                               \
+  if constexpr (kFold) {                                                     \
+    ha51 = hs * A51; ha52 = hs * A52; ha53 = hs * A53; ha54 = hs * A54;      \
+    ha61 = hs * A61; ha62 = hs * A62; ha63 = hs * A63; ha64 = hs * A64;      \
+    ha71 = hs * A71; ha73 = hs * A73; ha74 = hs * A74;                       \
+  }
+#define SBM_P6 if constexpr (kFold) { ha65 = hs * A65; ha75 = hs * A75; }
+#define SBM_P7 if constexpr (kFold) { ha76 = hs * A76; }
       SBM_ISSUE(t + C2 * hs, SBM_S2)
-      SBM_STAGE_THEN(t + C2 * hs, SBM_S2, k2, SBM_ISSUE(t + C3 * hs, SBM_S3))
-      SBM_STAGE_THEN(t + C3 * hs, SBM_S3, k3, SBM_ISSUE(t + C4 * hs, SBM_S4))
-      SBM_STAGE_THEN(t + C4 * hs, SBM_S4, k4, SBM_ISSUE(t + C5 * hs, SBM_S5))
-      SBM_STAGE_THEN(t + C5 * hs, SBM_S5, k5, SBM_ISSUE(t + hs, SBM_S6))
-      SBM_STAGE_THEN(t + hs, SBM_S6, k6, SBM_ISSUE(t + hs, SBM_S7))
+      SBM_STAGE_THEN(t + C2 * hs, SBM_S2, k2, SBM_P3 SBM_ISSUE(t + C3 * hs, SBM_S3))
+      SBM_STAGE_THEN(t + C3 * hs, SBM_S3, k3, SBM_P4 SBM_ISSUE(t + C4 * hs, SBM_S4))
+      SBM_STAGE_THEN(t + C4 * hs, SBM_S4, k4, SBM_P5 SBM_ISSUE(t + C5 * hs, SBM_S5))
+      SBM_STAGE_THEN(t + C5 * hs, SBM_S5, k5, SBM_P6 SBM_ISSUE(t + hs, SBM_S6))
+      SBM_STAGE_THEN(t + hs, SBM_S6, k6, SBM_P7 SBM_ISSUE(t + hs, SBM_S7))
       // zt is the 5th-order solution now.  k1 was last read when the input of stage 5 was formed, so
       // k7 = f(z_new) goes straight into it: an accepted step continues with it (FSAL, no copy), a
       // rejected one -- rare -- re-evaluates f(z).  One stage vector fewer alive through stages 5-7.
@@ -472,6 +518,11 @@ __device__ __forceinline__ SbmTrajOut sbm_dopri45(const Sys& sys, double (&z)[Sy
 #undef SBM_S5
 #undef SBM_S6
 #undef SBM_S7
+#undef SBM_P3
+#undef SBM_P4
+#undef SBM_P5
+#undef SBM_P6
+#undef SBM_P7
 
       // embedded error estimate h (E + e7 k7); ratios and norm in f32 (they only steer the controller).
       // The norm is homogeneous: |h| multiplies it once at the end instead of every element.
