@@ -116,10 +116,10 @@ def _locked_build(target, cmd_for, sources, what, force=False):
 
 
 def _core_sources():
-    srcs = [os.path.join(CSRC_DIR, f) for f in ('sbm_core.hip', 'sbm_plugin.h', 'sbm_sf_quadrature.hpp', 'sbm_ensemble_stats.hpp',
-                                                  'sbm_sampling_axes.hpp')]
-    srcs.append(os.path.join(REPO_DIR, 'include', 'sbm.h'))
-    return srcs
+    # every header of csrc/, as for the plugins: a new one cannot be missing from the stamp
+    return [os.path.join(CSRC_DIR, 'sbm_core.hip')] + \
+        sorted(os.path.join(CSRC_DIR, f) for f in os.listdir(CSRC_DIR) if f.endswith(('.hpp', '.h'))) + \
+        [os.path.join(REPO_DIR, 'include', 'sbm.h')]
 
 
 def build_core(force=False, extra_flags=()):

@@ -9,14 +9,17 @@
 //                     Jacobian (base_project.py:365-391,443-488; project/utils.py:10-89;
 //                     loss_functions/squared_loss/squared_loss_function.py:27-80;
 //                     linear_scale_factor.py:27-42)
-//   k_sf_entropy      scale-factor entropy integrals of a batch of simulations (linear_scale_factor.py:63-81)
-//   k_mh_propose / k_mh_accept   candidate move and Metropolis rule of the multi-chain sampler
-//                     (project/Ensembles.py:193-198, 260-264)
-//   k_sampling_axes / k_mh_accept_hastings   per-chain Hessian axes (batched Jacobi eigensolver + SloppyCell's clipping
-//                     recipe) and the Metropolis-Hastings rule of the sampler's second algorithm (sbm_sampling_axes.hpp;
-//                     project/Ensembles.py:153-157, 200-258)
-//   k_ens_*           statistics over the member axis of an ensemble of trajectories (sbm_ensemble_stats.hpp;
-//                     project/Ensembles.py:277-308, 335-361)
+// and the host side -- argument checks, LDS sizes, launches (launch_lds) -- of the kernels kept in headers of their own:
+//   sbm_lm.hpp              k_lm_step, k_lm_trust, k_lm_update, k_lm_accept: the fitting loop (batched Levenberg-Marquardt
+//                           step, lmder's trust-region step and bookkeeping)
+//   sbm_sampler.hpp         k_sf_entropy, k_mh_propose, k_mh_accept, k_mh_accept_hastings: scale-factor entropy integrals
+//                           (linear_scale_factor.py:63-81; the quadrature rule: sbm_sf_quadrature.hpp), candidate move and
+//                           the two acceptance rules of the multi-chain sampler (project/Ensembles.py:193-198, 200-264)
+//   sbm_sampling_axes.hpp   k_sampling_axes: per-chain Hessian axes (batched Jacobi eigensolver + SloppyCell's clipping
+//                           recipe; project/Ensembles.py:153-157)
+//   sbm_ensemble_stats.hpp  k_ens_*: statistics over the member axis of an ensemble of trajectories
+//                           (project/Ensembles.py:277-308, 335-361)
+//   sbm_block_reduce.hpp    the wavefront / workgroup reductions that k_assemble, the fitting and the sampler kernels share
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <stdarg.h>
@@ -28,8 +31,10 @@
 #include <vector>
 
 #include "sbm_plugin.h"
-#include "sbm_sf_quadrature.hpp"
+#include "sbm_block_reduce.hpp"
 #include "sbm_ensemble_stats.hpp"
+#include "sbm_lm.hpp"
+#include "sbm_sampler.hpp"
 #include "sbm_sampling_axes.hpp"
 
 // ---------------------------------------------------------------------------
@@ -471,24 +476,6 @@ __global__ void k_fill_grids(const int32_t* __restrict__ tgrid_off, int V, int E
   const int e = idx % E;
   goff[idx] = tgrid_off[e];
   glen[idx] = tgrid_off[e + 1] - tgrid_off[e];
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ double block_sum(double v, double* red /*[4]*/) {
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  double s = 0.0;
-  const int nw = blockDim.x >> 6;
-  for (int i = 0; i < nw; ++i) s += red[i];
-  return s;
 }
 
 struct AssembleArgs {
@@ -1318,446 +1305,38 @@ extern "C" int sbm_loss_eval_host(sbm_ctx* ctx, const sbm_loss_desc* d, int32_t 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Batched Levenberg-Marquardt step (the caller after the path: multi-start fitting).
-// The reference fits with scipy.optimize.leastsq(project.residuals, x0, Dfun=project.calc_project_jacobian)
-// (tests/test_Project.py:202-213, :352-357), one start at a time; here every parameter vector of an
-// ensemble takes its own damped Gauss-Newton step:
-//     (J^T J + lambda_v diag(J^T J)) delta_v = -J^T r_v          (Marquardt scaling)
-// One 256-thread block per vector: J^T J and J^T r accumulated from row tiles staged in LDS,
-// Cholesky and the two triangular solves in LDS.  q <= 128.
+// Kernels with dynamic LDS: what a workgroup may have, and the launch.
 // ---------------------------------------------------------------------------------------------
-struct LmArgs {
-  const double* J;       // [V][M][q]
-  const double* r;       // [V][M]
-  const double* lambda;  // [V]
-  double* delta;         // [V][q]
-  double* pred;          // [V] predicted decrease of 0.5 |r|^2: -g.delta - 0.5 delta^T (J^T J) delta
-  int32_t* status;       // [V] 0 ok, 1 not positive definite / non-finite input (delta = 0)
-  int M, q, tile;
-};
-
-constexpr int LM_TILE = 32;   // rows of J staged per pass (fewer when the q x q matrix leaves less room: lm_lds_bytes)
-
-// LDS of the normal-equation kernels: the q x (q + 1) matrix, `nvec` vectors of q, a row tile of J with the residuals
-// beside it.  The tile shrinks (32, 16, 8 rows) until the total fits what the device gives a workgroup; 0 = no fit.
 static int lm_lds_limit(sbm_ctx* ctx) {
   int lim = 0;
   if (hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess || lim <= 0) lim = 64 * 1024;
   return lim;
 }
-static size_t lm_lds_bytes(sbm_ctx* ctx, int q, int nvec, int* tile_out) {
-  const size_t ld = (size_t)q + 1;
-  const size_t limit = (size_t)lm_lds_limit(ctx);
-  for (int tile = LM_TILE; tile >= 8; tile /= 2) {
-    const size_t b = sizeof(double) * ((size_t)q * ld + (size_t)nvec * q + (size_t)tile * ld + tile);
-    if (b <= limit) { *tile_out = tile; return b; }
-  }
-  return 0;
-}
 
-__global__ void __launch_bounds__(256) k_lm_step(LmArgs a) {
-  extern __shared__ __attribute__((aligned(16))) double lm_smem[];
-  const int v = blockIdx.x, tid = threadIdx.x, q = a.q, M = a.M;
-  const int ld = q + 1;                      // padded leading dimension of the q x q matrices
-  double* A = lm_smem;                       // [q][ld]  J^T J, then its Cholesky factor (lower)
-  double* dg = A + (size_t)q * ld;           // [q]      diag(J^T J)
-  double* g = dg + q;                        // [q]      J^T r
-  double* x = g + q;                         // [q]      right-hand side, then the solution
-  const int TILE = a.tile;
-  double* T = x + q;                         // [TILE][ld] row tile of J
-  double* rt = T + (size_t)TILE * ld;        // [TILE]
-  __shared__ int s_bad;
-  if (tid == 0) s_bad = 0;
-  const double* Jv = a.J + (size_t)v * M * q;
-  const double* rv = a.r + (size_t)v * M;
-  // each thread owns the entries e = tid, tid + 256, ... of the lower triangle (i >= j) and of g
-  const int n_low = q * (q + 1) / 2;
-  constexpr int MAXOWN = (128 * 129 / 2 + 255) / 256;
-  double acc[MAXOWN];
-  int oi[MAXOWN], oj[MAXOWN];
-  int n_own = 0;
-  for (int e = tid; e < n_low; e += 256) {
-    // row i with i(i+1)/2 <= e
-    int i = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-    while ((i + 1) * (i + 2) / 2 <= e) ++i;
-    while (i * (i + 1) / 2 > e) --i;
-    oi[n_own] = i; oj[n_own] = e - i * (i + 1) / 2; acc[n_own] = 0.0; ++n_own;
-  }
-  double gacc = 0.0;   // thread c < q owns g[c]
-  for (int m0 = 0; m0 < M; m0 += TILE) {
-    const int rows = min(TILE, M - m0);
-    __syncthreads();
-    for (int e = tid; e < rows * q; e += 256) {
-      const int rr = e / q, c = e - rr * q;
-      const double val = Jv[(size_t)(m0 + rr) * q + c];
-      T[rr * ld + c] = val;
-      if (!(fabs(val) < 1.0e300)) s_bad = 1;
-    }
-    for (int e = tid; e < rows; e += 256) {
-      const double val = rv[m0 + e];
-      rt[e] = val;
-      if (!(fabs(val) < 1.0e300)) s_bad = 1;
-    }
-    __syncthreads();
-    for (int k = 0; k < n_own; ++k) {
-      double s = acc[k];
-      for (int rr = 0; rr < rows; ++rr) s = fma(T[rr * ld + oi[k]], T[rr * ld + oj[k]], s);
-      acc[k] = s;
-    }
-    if (tid < q) {
-      double s = gacc;
-      for (int rr = 0; rr < rows; ++rr) s = fma(T[rr * ld + tid], rt[rr], s);
-      gacc = s;
-    }
-  }
-  __syncthreads();
-  for (int k = 0; k < n_own; ++k) A[oi[k] * ld + oj[k]] = acc[k];
-  if (tid < q) g[tid] = gacc;
-  __syncthreads();
-  const double lam = a.lambda[v];
-  if (tid < q) {
-    const double d = A[tid * ld + tid];
-    dg[tid] = d;
-    // Marquardt scaling; a column J never touches (d = 0) gets a unit pivot: delta_c = 0
-    A[tid * ld + tid] = d > 0.0 ? d * (1.0 + lam) : 1.0;
-    x[tid] = -g[tid];
-  }
-  __syncthreads();
-  bool bad = s_bad != 0 || !(lam >= 0.0);
-  // right-looking Cholesky, lower triangle in place
-  for (int k = 0; k < q && !bad; ++k) {
-    const double piv = A[k * ld + k];
-    if (!(piv > 0.0) || !(piv < 1.0e300)) { bad = true; break; }   // uniform: every thread reads the same value
-    const double rp = 1.0 / sqrt(piv);
-    __syncthreads();
-    if (tid == 0) A[k * ld + k] = sqrt(piv);
-    for (int i = k + 1 + tid; i < q; i += 256) A[i * ld + k] *= rp;
-    __syncthreads();
-    // trailing update: entries (i, j), k < j <= i
-    const int nt = q - k - 1;
-    for (int e = tid; e < nt * nt; e += 256) {
-      const int i = k + 1 + e / nt, j = k + 1 + e % nt;
-      if (j <= i) A[i * ld + j] = fma(-A[i * ld + k], A[j * ld + k], A[i * ld + j]);
-    }
-    __syncthreads();
-  }
-  if (bad) {
-    for (int c = tid; c < q; c += 256) a.delta[(size_t)v * q + c] = 0.0;
-    if (tid == 0) { a.pred[v] = 0.0; a.status[v] = 1; }
-    return;
-  }
-  // L y = -g, then L^T x = y, column-oriented: one thread finishes x_i, all threads retire it from the
-  // remaining right-hand sides (two barriers per column instead of a serial O(q^2) chain on one thread)
-  for (int i = 0; i < q; ++i) {
-    if (tid == 0) x[i] /= A[i * ld + i];
-    __syncthreads();
-    const double xi = x[i];
-    for (int j = i + 1 + tid; j < q; j += 256) x[j] = fma(-A[j * ld + i], xi, x[j]);
-    __syncthreads();
-  }
-  for (int i = q - 1; i >= 0; --i) {
-    if (tid == 0) x[i] /= A[i * ld + i];
-    __syncthreads();
-    const double xi = x[i];
-    for (int j = tid; j < i; j += 256) x[j] = fma(-A[i * ld + j], xi, x[j]);
-    __syncthreads();
-  }
-  // predicted decrease of 0.5 |r|^2 under the Gauss-Newton model, H = J^T J:  -g.d - 0.5 d^T H d  with
-  // (H + lambda D) d = -g  =>  d^T H d = -g.d - lambda sum D_i d_i^2   (D = diag(H), or 1 where it is 0)
-  double part = 0.0;
-  if (tid < q) {
-    a.delta[(size_t)v * q + tid] = x[tid];
-    const double Di = dg[tid] > 0.0 ? dg[tid] : 0.0;
-    part = -0.5 * g[tid] * x[tid] + 0.5 * lam * Di * x[tid] * x[tid];
-  }
-  __shared__ double s_red[4];
-  const double tot = block_sum(part, s_red);
-  if (tid == 0) { a.pred[v] = tot; a.status[v] = 0; }
-}
-
-extern "C" int sbm_lm_step(sbm_ctx* ctx, const double* J, const double* r, const double* lambda, int32_t V, int32_t M,
-                           int32_t q, double* delta, double* pred, int32_t* status) {
-  if (!ctx || !J || !r || !lambda || !delta || !pred || !status) return sbm_fail(SBM_E_ARG, "sbm_lm_step: NULL argument");
-  if (V < 0 || M <= 0 || q <= 0 || q > 128) return sbm_fail(SBM_E_ARG, "sbm_lm_step: bad sizes V=%d M=%d q=%d (q <= 128)", V, M, q);
-  if (V == 0) return 0;
+// `kernel` on the context's device and stream with `lds` bytes of dynamic LDS; more than 64 KB have to be asked for
+template <class... P, class... A>
+static int launch_lds(sbm_ctx* ctx, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, const A&... args) {
   SBM_HIP(hipSetDevice(ctx->device));
-  const size_t ld = (size_t)q + 1;
-  int tile = 0;
-  const size_t lds = lm_lds_bytes(ctx, q, 3, &tile);
-  if (!lds) return sbm_fail(SBM_E_ARG, "sbm_lm_step: q = %d does not fit the %d KB of LDS of a workgroup", q, lm_lds_limit(ctx) / 1024);
-  LmArgs a{J, r, lambda, delta, pred, status, M, q, tile};
-  (void)ld;
-  if (lds > 64 * 1024) SBM_HIP(hipFuncSetAttribute((const void*)k_lm_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_lm_step, dim3(V), dim3(256), lds, ctx->stream, a);
+  if (lds > 64 * 1024) SBM_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, args...);
   SBM_HIP(hipGetLastError());
   return 0;
 }
 
 // ---------------------------------------------------------------------------------------------
-// sbm_lm_trust_step: the Levenberg-Marquardt PARAMETER of a scaled trust region, per vector.
-//
-// What MINPACK's lmder does between two Jacobian evaluations (lmpar, More 1978), on the normal equations:
-// given the scaling D (the largest column norm of J seen so far, kept by the caller from call to call) and a radius
-// Delta, find lambda >= 0 with  (J^T J + lambda D^2) x = -J^T r  and  | ||D x|| - Delta | <= 0.1 Delta  (lambda = 0 if
-// the Gauss-Newton step is already inside), by More's safeguarded Newton iteration on
-// phi(lambda) = ||D x(lambda)|| - Delta:  lambda += (phi / Delta) / ||L^-1 D^2 x / ||D x||||^2  with L the Cholesky
-// factor of the damped matrix, kept between the bounds the iteration itself produces.  At most 10 factorisations of a
-// q x q matrix per call (two to three are the rule): microseconds, against the milliseconds of the integration that
-// follows -- which is why the search for lambda happens here, in one launch, rather than as a sequence of trial
-// INTEGRATIONS with lambda multiplied up and down (sbm_lm_step + project/fitting.py's 'marquardt' loop).
-// One 256-thread block per vector; J^T J in registers (the lower triangle, spread over the threads), the matrix being
-// factored in LDS.
+// The fitting loop (kernels: sbm_lm.hpp): the batched Levenberg-Marquardt step, the trust-region step with lmder's
+// search for the Levenberg-Marquardt parameter, and lmder's bookkeeping between two steps.
 // ---------------------------------------------------------------------------------------------
-struct LmTrustArgs {
-  const double* J;       // [V][M][q]
-  const double* r;       // [V][M]
-  double* dscale;        // [V][q]  in / out: D, made max(D, column norm of J) here (0 on the first call)
-  const double* radius;  // [V]     Delta > 0
-  double* lambda;        // [V]     in: the previous parameter (a starting guess), out: the one found
-  double* delta;         // [V][q]  out: x
-  double* pred;          // [V]     out: predicted decrease of 0.5 |r|^2 = -g.x - 0.5 x^T J^T J x
-  double* dxnorm;        // [V]     out: ||D x||
-  int32_t* status;       // [V]     out: 0, 1: non-finite input / no positive definite system found (x = 0), 2: skipped
-  int M, q, tile;
-  // extended entry point (sbm_lm_trust_step_ex); all nullable / 0
-  const double* row_scale;   // [M]    J is used as diag(row_scale) J (reference_compat Jacobians: 1 / sigma)
-  const int32_t* skip;       // [V]    != 0: leave the vector alone (x = 0, status 2)
-  double max_step;           // > 0: every component of x is clipped to +-max_step; pred, dxnorm, gtx are those of the clipped step
-  double* gtx;               // [V]    out: g . x (the directional derivative of 0.5 |r|^2 along the step)
-  const double* theta;       // [V][q] with `trial`: trial = theta + x
-  double* trial;             // [V][q]
-};
-
-
-// in-place Cholesky of the lower triangle of A (q x q, leading dimension ld) by the whole block; false if a pivot is
-// not positive (the decision is uniform: every thread reads the same pivot)
-__device__ __forceinline__ bool lm_cholesky(double* A, int q, int ld, int tid) {
-  for (int k = 0; k < q; ++k) {
-    const double piv = A[k * ld + k];
-    if (!(piv > 0.0) || !(piv < 1.0e300)) return false;
-    const double rp = 1.0 / sqrt(piv);
-    __syncthreads();
-    if (tid == 0) A[k * ld + k] = sqrt(piv);
-    for (int i = k + 1 + tid; i < q; i += 256) A[i * ld + k] *= rp;
-    __syncthreads();
-    const int nt = q - k - 1;
-    for (int e = tid; e < nt * nt; e += 256) {
-      const int i = k + 1 + e / nt, j = k + 1 + e % nt;
-      if (j <= i) A[i * ld + j] = fma(-A[i * ld + k], A[j * ld + k], A[i * ld + j]);
-    }
-    __syncthreads();
-  }
-  return true;
-}
-// x <- L^-1 x (column-oriented: one thread finishes x_i, all retire it from the rest)
-__device__ __forceinline__ void lm_forward(const double* A, double* x, int q, int ld, int tid) {
-  for (int i = 0; i < q; ++i) {
-    if (tid == 0) x[i] /= A[i * ld + i];
-    __syncthreads();
-    const double xi = x[i];
-    for (int j = i + 1 + tid; j < q; j += 256) x[j] = fma(-A[j * ld + i], xi, x[j]);
-    __syncthreads();
-  }
-}
-// x <- L^-T x
-__device__ __forceinline__ void lm_backward(const double* A, double* x, int q, int ld, int tid) {
-  for (int i = q - 1; i >= 0; --i) {
-    if (tid == 0) x[i] /= A[i * ld + i];
-    __syncthreads();
-    const double xi = x[i];
-    for (int j = tid; j < i; j += 256) x[j] = fma(-A[i * ld + j], xi, x[j]);
-    __syncthreads();
-  }
-}
-
-__global__ void __launch_bounds__(256) k_lm_trust(LmTrustArgs a) {
-  extern __shared__ __attribute__((aligned(16))) double lm_smem[];
-  const int v = blockIdx.x, tid = threadIdx.x, q = a.q, M = a.M, TILE = a.tile;
-  const int ld = q + 1;
-  double* A = lm_smem;                       // [q][ld]  the damped matrix / its Cholesky factor
-  double* D = A + (size_t)q * ld;            // [q]      scaling
-  double* g = D + q;                         // [q]      J^T r
-  double* x = g + q;                         // [q]      step
-  double* w = x + q;                         // [q]      work vector of the Newton correction
-  double* xg = w + q;                        // [q]      the last step that came out of a successful factorisation
-  double* T = xg + q;                        // [TILE][ld] row tile of J
-  double* rt = T + (size_t)TILE * ld;        // [TILE]
-  __shared__ int s_bad;
-  __shared__ double s_red[4];
-  if (a.skip && a.skip[v]) {
-    for (int c = tid; c < q; c += 256) {
-      a.delta[(size_t)v * q + c] = 0.0;
-      if (a.trial && a.theta) a.trial[(size_t)v * q + c] = a.theta[(size_t)v * q + c];
-    }
-    if (tid == 0) { a.pred[v] = 0.0; a.dxnorm[v] = 0.0; a.status[v] = 2; if (a.gtx) a.gtx[v] = 0.0; }
-    return;
-  }
-  if (tid == 0) s_bad = 0;
-  const double* Jv = a.J + (size_t)v * M * q;
-  const double* rv = a.r + (size_t)v * M;
-  const int n_low = q * (q + 1) / 2;
-  constexpr int MAXOWN = (128 * 129 / 2 + 255) / 256;
-  double acc[MAXOWN];
-  int oi[MAXOWN], oj[MAXOWN];
-  int n_own = 0;
-  for (int e = tid; e < n_low; e += 256) {
-    int i = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-    while ((i + 1) * (i + 2) / 2 <= e) ++i;
-    while (i * (i + 1) / 2 > e) --i;
-    oi[n_own] = i; oj[n_own] = e - i * (i + 1) / 2; acc[n_own] = 0.0; ++n_own;
-  }
-  double gacc = 0.0;
-  for (int m0 = 0; m0 < M; m0 += TILE) {
-    const int rows = min(TILE, M - m0);
-    __syncthreads();
-    for (int e = tid; e < rows * q; e += 256) {
-      const int rr = e / q, c = e - rr * q;
-      double val = Jv[(size_t)(m0 + rr) * q + c];
-      if (a.row_scale) val *= a.row_scale[m0 + rr];
-      T[rr * ld + c] = val;
-      if (!(fabs(val) < 1.0e300)) s_bad = 1;
-    }
-    for (int e = tid; e < rows; e += 256) {
-      const double val = rv[m0 + e];
-      rt[e] = val;
-      if (!(fabs(val) < 1.0e300)) s_bad = 1;
-    }
-    __syncthreads();
-    for (int k = 0; k < n_own; ++k) {
-      double sacc = acc[k];
-      for (int rr = 0; rr < rows; ++rr) sacc = fma(T[rr * ld + oi[k]], T[rr * ld + oj[k]], sacc);
-      acc[k] = sacc;
-    }
-    if (tid < q) {
-      double sacc = gacc;
-      for (int rr = 0; rr < rows; ++rr) sacc = fma(T[rr * ld + tid], rt[rr], sacc);
-      gacc = sacc;
-    }
-  }
-  __syncthreads();
-  const double Delta = a.radius[v];
-  double lam = a.lambda[v];
-  // scaling: the largest column norm seen so far (MINPACK mode 1); a column J never touches gets 1
-  for (int k = 0; k < n_own; ++k)
-    if (oi[k] == oj[k]) {
-      const double cn = sqrt(fmax(acc[k], 0.0));
-      double d = fmax(a.dscale[(size_t)v * q + oi[k]], cn);
-      if (!(d > 0.0)) d = 1.0;
-      D[oi[k]] = d;
-      a.dscale[(size_t)v * q + oi[k]] = d;
-    }
-  if (tid < q) g[tid] = gacc;
-  __syncthreads();
-  bool bad = s_bad != 0 || !(Delta > 0.0) || !(lam >= 0.0);
-  // paru = || D^-1 g || / Delta: with that much damping the step is inside the region
-  double part = 0.0;
-  if (tid < q) { const double t = g[tid] / D[tid]; part = t * t; }
-  const double gnorm = sqrt(block_sum(part, s_red));
-  double paru = gnorm / Delta;
-  if (!(paru > 0.0)) paru = 2.2e-308 / fmin(Delta, 0.1);
-  double parl = 0.0, fp = 0.0, dxn = 0.0;
-  bool have = false;
-  double lam_good = 0.0, dxn_good = 0.0;      // ... of the last successful factorisation (its step is parked in xg)
-
-  auto solve_with = [&](double par) -> bool {          // A <- chol(J^T J + par D^2); x <- -A^-1 g; dxn, fp
-    for (int k = 0; k < n_own; ++k) {
-      const int i = oi[k], j = oj[k];
-      A[i * ld + j] = (i == j) ? fma(par * D[i], D[i], acc[k]) : acc[k];
-    }
-    if (tid < q) x[tid] = -g[tid];
-    __syncthreads();
-    if (!lm_cholesky(A, q, ld, tid)) return false;
-    lm_forward(A, x, q, ld, tid);
-    lm_backward(A, x, q, ld, tid);
-    double p2 = 0.0;
-    if (tid < q) { const double t = D[tid] * x[tid]; p2 = t * t; xg[tid] = x[tid]; }
-    dxn = sqrt(block_sum(p2, s_red));
-    fp = dxn - Delta;
-    lam_good = par;
-    dxn_good = dxn;
-    return true;
-  };
-  auto newton_denominator = [&]() -> double {           // || L^-1 (D^2 x / dxn) ||^2 with the current factor
-    if (tid < q) w[tid] = D[tid] * D[tid] * x[tid] / dxn;
-    __syncthreads();
-    lm_forward(A, w, q, ld, tid);
-    double p2 = 0.0;
-    if (tid < q) p2 = w[tid] * w[tid];
-    return block_sum(p2, s_red);
-  };
-
-  if (!bad) {
-    // the Gauss-Newton step, if J has full rank numerically
-    if (solve_with(0.0)) {
-      if (fp <= 0.1 * Delta) { lam = 0.0; have = true; }
-      else { const double den = newton_denominator(); if (den > 0.0) parl = (fp / Delta) / den; }
-    }
-    if (!have) {
-      bool any = false;                                // a damped system has been solved
-      lam = fmin(fmax(lam, parl), paru);
-      if (lam == 0.0) lam = (dxn > 0.0) ? gnorm / dxn : 1.0e-3 * paru;
-      for (int it = 0; it < 10; ++it) {
-        if (lam == 0.0) lam = fmax(2.2e-308, 1.0e-3 * paru);
-        const double fp_old = fp;
-        if (!solve_with(lam)) {                        // rounding: not positive definite at this damping yet
-          // A is half factored and x holds -g: what counts from here on is the last step that WAS solved for (xg)
-          parl = fmax(parl, lam);
-          lam = fmax(10.0 * lam, 1.0e-3 * paru);
-          if (lam > 1.0e3 * paru) break;               // (only non-finite data gets here)
-          continue;
-        }
-        any = true;
-        if (fabs(fp) <= 0.1 * Delta || (parl == 0.0 && fp <= fp_old && fp_old < 0.0) || it == 9) break;
-        const double den = newton_denominator();
-        const double parc = den > 0.0 ? (fp / Delta) / den : 0.0;
-        if (fp > 0.0) parl = fmax(parl, lam);
-        if (fp < 0.0) paru = fmin(paru, lam);
-        lam = fmax(parl, lam + parc);
-      }
-      // the answer is the last DAMPED system that factored -- never the right-hand side a failed factorisation left
-      // in x, nor the undamped step that was outside the region
-      have = any && lam_good > 0.0;
-      if (have) { lam = lam_good; dxn = dxn_good; }
-      __syncthreads();
-      if (have && tid < q) x[tid] = xg[tid];
-      __syncthreads();
-    }
-  }
-  if (bad || !have) {
-    for (int c = tid; c < q; c += 256) {
-      a.delta[(size_t)v * q + c] = 0.0;
-      if (a.trial && a.theta) a.trial[(size_t)v * q + c] = a.theta[(size_t)v * q + c];
-    }
-    if (tid == 0) { a.pred[v] = 0.0; a.dxnorm[v] = 0.0; a.status[v] = 1; if (a.gtx) a.gtx[v] = 0.0; }
-    return;
-  }
-  // a step bound per component (exp(theta) has to stay finite): clip, and report the quantities of the step TAKEN
-  bool clipped = false;
-  if (a.max_step > 0.0) {
-    int cl = 0;
-    if (tid < q && fabs(x[tid]) > a.max_step) { x[tid] = copysign(a.max_step, x[tid]); cl = 1; }
-    clipped = __syncthreads_or(cl) != 0;
-  }
-  double gx = 0.0;
-  if (tid < q) gx = g[tid] * x[tid];
-  const double gtx = block_sum(gx, s_red);
-  double tot;
-  if (!clipped) {
-    // predicted decrease of 0.5 |r|^2 under the Gauss-Newton model:  -g.x - 0.5 x^T H x  with  x^T H x = -g.x - lam dxn^2
-    tot = -0.5 * gtx + 0.5 * lam * dxn * dxn;
-  } else {
-    double p2 = 0.0;
-    if (tid < q) { const double t = D[tid] * x[tid]; p2 = t * t; }
-    dxn = sqrt(block_sum(p2, s_red));
-    double xhx = 0.0;                                  // x^T (J^T J) x from the lower triangle in registers
-    for (int k = 0; k < n_own; ++k) xhx += (oi[k] == oj[k] ? 1.0 : 2.0) * acc[k] * x[oi[k]] * x[oj[k]];
-    tot = -gtx - 0.5 * block_sum(xhx, s_red);
-  }
-  if (tid < q) {
-    a.delta[(size_t)v * q + tid] = x[tid];
-    if (a.trial && a.theta) a.trial[(size_t)v * q + tid] = a.theta[(size_t)v * q + tid] + x[tid];
-  }
-  if (tid == 0) { a.pred[v] = tot; a.dxnorm[v] = dxn; a.lambda[v] = lam; a.status[v] = 0; if (a.gtx) a.gtx[v] = gtx; }
+extern "C" int sbm_lm_step(sbm_ctx* ctx, const double* J, const double* r, const double* lambda, int32_t V, int32_t M,
+                           int32_t q, double* delta, double* pred, int32_t* status) {
+  if (!ctx || !J || !r || !lambda || !delta || !pred || !status) return sbm_fail(SBM_E_ARG, "sbm_lm_step: NULL argument");
+  if (V < 0 || M <= 0 || q <= 0 || q > LM_MAX_Q) return sbm_fail(SBM_E_ARG, "sbm_lm_step: bad sizes V=%d M=%d q=%d (q <= %d)", V, M, q, LM_MAX_Q);
+  if (V == 0) return 0;
+  int tile = 0;
+  const size_t lds = lm_lds_bytes(q, 3, (size_t)lm_lds_limit(ctx), &tile);
+  if (!lds) return sbm_fail(SBM_E_ARG, "sbm_lm_step: q = %d does not fit the %d KB of LDS of a workgroup", q, lm_lds_limit(ctx) / 1024);
+  LmArgs a{J, r, lambda, delta, pred, status, M, q, tile};
+  return launch_lds(ctx, k_lm_step, dim3(V), dim3(256), lds, a);
 }
 
 extern "C" int sbm_lm_trust_step_ex(sbm_ctx* ctx, const double* J, const double* r, double* dscale, const double* radius,
@@ -1766,18 +1345,14 @@ extern "C" int sbm_lm_trust_step_ex(sbm_ctx* ctx, const double* J, const double*
                                     double* pred, double* dxnorm, double* gtx, int32_t* status) {
   if (!ctx || !J || !r || !dscale || !radius || !lambda || !delta || !pred || !dxnorm || !status)
     return sbm_fail(SBM_E_ARG, "sbm_lm_trust_step: NULL argument");
-  if (V < 0 || M <= 0 || q <= 0 || q > 128) return sbm_fail(SBM_E_ARG, "sbm_lm_trust_step: bad sizes V=%d M=%d q=%d (q <= 128)", V, M, q);
+  if (V < 0 || M <= 0 || q <= 0 || q > LM_MAX_Q) return sbm_fail(SBM_E_ARG, "sbm_lm_trust_step: bad sizes V=%d M=%d q=%d (q <= %d)", V, M, q, LM_MAX_Q);
   if ((theta == nullptr) != (trial == nullptr)) return sbm_fail(SBM_E_ARG, "sbm_lm_trust_step_ex: theta and trial go together");
   if (V == 0) return 0;
-  SBM_HIP(hipSetDevice(ctx->device));
   int tile = 0;
-  const size_t lds = lm_lds_bytes(ctx, q, 5, &tile);
+  const size_t lds = lm_lds_bytes(q, 5, (size_t)lm_lds_limit(ctx), &tile);
   if (!lds) return sbm_fail(SBM_E_ARG, "sbm_lm_trust_step: q = %d does not fit the %d KB of LDS of a workgroup", q, lm_lds_limit(ctx) / 1024);
   LmTrustArgs a{J, r, dscale, radius, lambda, delta, pred, dxnorm, status, M, q, tile, row_scale, skip, max_step, gtx, theta, trial};
-  if (lds > 64 * 1024) SBM_HIP(hipFuncSetAttribute((const void*)k_lm_trust, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_lm_trust, dim3(V), dim3(256), lds, ctx->stream, a);
-  SBM_HIP(hipGetLastError());
-  return 0;
+  return launch_lds(ctx, k_lm_trust, dim3(V), dim3(256), lds, a);
 }
 
 extern "C" int sbm_lm_trust_step(sbm_ctx* ctx, const double* J, const double* r, double* dscale, const double* radius,
@@ -1785,88 +1360,6 @@ extern "C" int sbm_lm_trust_step(sbm_ctx* ctx, const double* J, const double* r,
                                  double* dxnorm, int32_t* status) {
   return sbm_lm_trust_step_ex(ctx, J, r, dscale, radius, lambda, V, M, q, nullptr, nullptr, 0.0, nullptr, nullptr, delta, pred,
                               dxnorm, nullptr, status);
-}
-
-// ---------------------------------------------------------------------------------------------
-// sbm_lm_update / sbm_lm_accept: lmder's bookkeeping between two trust-region steps, for V starts in two launches
-// (round 2 spelled it as ~70 tensor selects per iteration: 68 000 micro-launches in a 100-iteration fit).
-// ---------------------------------------------------------------------------------------------
-struct LmUpdateArgs {
-  const double* cost;       // [V] 0.5 |r|^2 at the current point (inf: a start that cannot be integrated)
-  const double* norms_t;    // [V] |r|^2 at the trial point
-  const int32_t* status_t;  // [V] integration status of the trial point (non-zero: failed)
-  const double* pred;       // [V] from sbm_lm_trust_step_ex
-  const double* dxnorm;     // [V]
-  const double* gtx;        // [V]
-  const int32_t* st;        // [V] status of the trust step (0 ok, 1 no system solved, 2 skipped)
-  const double* theta;      // [V][q] current point (for ||D theta||)
-  const double* dscale;     // [V][q]
-  double* radius;           // [V] in / out
-  double* lambda;           // [V] in / out
-  int32_t* done;            // [V] in / out: 1 = converged (or never started)
-  int32_t* accept;          // [V] out: 1 = take the trial point
-  int32_t* n_iter;          // [V] in / out: iteration at which the start converged
-  int32_t* counters;        // [2] out: starts still running, trial points accepted (zeroed by the caller's memset)
-  double* ratio_out;        // [V] nullable: actual / predicted reduction (traces)
-  double ftol, xtol;
-  int V, q, iteration, first;
-};
-
-__global__ void __launch_bounds__(256) k_lm_update(LmUpdateArgs a) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= a.V) return;
-  a.accept[v] = 0;
-  if (a.done[v]) return;
-  const double cost = a.cost[v];
-  double cost_t = 0.5 * a.norms_t[v];
-  if (!(cost_t < 1.0e300) || a.status_t[v] != 0) cost_t = __builtin_inf();
-  const int st = a.st[v];
-  double radius = a.radius[v], lam = a.lambda[v];
-  const double dxn = a.dxnorm[v];
-  if (a.first && st == 0) radius = fmin(radius, dxn);          // lmder: on the first iteration Delta = min(Delta, ||D p||)
-  // lmder's quantities, relative to |r|^2 = 2 cost
-  const double safe = cost > 0.0 ? cost : 1.0;
-  const bool not_10x_worse = 0.1 * sqrt(cost_t) < sqrt(cost);   // (false for an infinite trial cost)
-  const double actred = not_10x_worse ? 1.0 - cost_t / safe : -1.0;
-  const double prered = a.pred[v] / safe;
-  const double dirder = a.gtx[v] / (2.0 * safe);               // g . p / |r|^2 (= -(|J p|^2 + lam |D p|^2) / |r|^2 for an unclipped step)
-  const double ratio = prered > 0.0 ? actred / prered : 0.0;
-  if (a.ratio_out) a.ratio_out[v] = ratio;
-  if (st != 0) {
-    // no system could be solved: halve the radius, keep the point
-    a.radius[v] = 0.5 * radius;
-    atomicAdd(a.counters, 1);
-    return;
-  }
-  if (ratio <= 0.25) {
-    double temp = actred >= 0.0 ? 0.5 : 0.5 * dirder / ((dirder + 0.5 * actred) != 0.0 ? dirder + 0.5 * actred : -1.0);
-    if (!not_10x_worse || temp < 0.1 || !(temp == temp) || !(fabs(temp) < 1.0e300)) temp = 0.1;
-    radius = temp * fmin(radius, dxn / 0.1);
-    lam = lam / temp;
-  } else if (lam == 0.0 || ratio >= 0.75) {
-    radius = dxn / 0.5;
-    lam = 0.5 * lam;
-  }
-  const bool ok = ratio >= 1.0e-4 && cost_t < 1.0e300;
-  a.accept[v] = ok ? 1 : 0;
-  // lmder's convergence tests (info 1, 2); ||D theta|| at the point the iteration started from (the current point, before
-  // sbm_lm_accept moves it: lmder itself measures the point it ends on)
-  double xn2 = 0.0;
-  for (int c = 0; c < a.q; ++c) {
-    const double t = a.dscale[(size_t)v * a.q + c] * a.theta[(size_t)v * a.q + c];
-    xn2 = fma(t, t, xn2);
-  }
-  const bool conv_f = fabs(actred) <= a.ftol && prered <= a.ftol && 0.5 * ratio <= 1.0;
-  const bool conv_x = radius <= a.xtol * sqrt(xn2);
-  a.radius[v] = radius;
-  a.lambda[v] = lam;
-  if (conv_f || conv_x) {
-    a.done[v] = 1;
-    a.n_iter[v] = a.iteration + 1;
-  } else {
-    atomicAdd(a.counters, 1);
-  }
-  if (ok) atomicAdd(a.counters + 1, 1);
 }
 
 extern "C" int sbm_lm_update(sbm_ctx* ctx, const double* cost, const double* norms_trial, const int32_t* status_trial,
@@ -1888,31 +1381,6 @@ extern "C" int sbm_lm_update(sbm_ctx* ctx, const double* cost, const double* nor
   return 0;
 }
 
-// accepted trial points become the current ones: theta, residuals, Jacobian (scaled by row_scale if given), cost
-__global__ void __launch_bounds__(256) k_lm_accept(const int32_t* __restrict__ accept, int q, int M, const double* __restrict__ trial,
-                                                   const double* __restrict__ r_t, const double* __restrict__ J_t,
-                                                   const double* __restrict__ norms_t, double* __restrict__ theta,
-                                                   double* __restrict__ r, double* __restrict__ J, double* __restrict__ cost) {
-  const int v = blockIdx.x;
-  if (!accept[v]) return;
-  const size_t nJ = (size_t)M * q;
-  const double2* src = reinterpret_cast<const double2*>(J_t + (size_t)v * nJ);
-  double2* dst = reinterpret_cast<double2*>(J + (size_t)v * nJ);
-  // 16-byte accesses only where both rows really are 16-byte aligned: an even row length and element offset say nothing
-  // about the base pointers (a view that starts one double into an allocation is 8-byte aligned)
-  if ((nJ & 1) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
-    for (size_t e = threadIdx.x + (size_t)blockIdx.y * blockDim.x; e < nJ / 2; e += (size_t)blockDim.x * gridDim.y) dst[e] = src[e];
-  } else {
-    for (size_t e = threadIdx.x + (size_t)blockIdx.y * blockDim.x; e < nJ; e += (size_t)blockDim.x * gridDim.y)
-      J[(size_t)v * nJ + e] = J_t[(size_t)v * nJ + e];
-  }
-  if (blockIdx.y == 0) {
-    for (int e = threadIdx.x; e < M; e += blockDim.x) r[(size_t)v * M + e] = r_t[(size_t)v * M + e];
-    for (int e = threadIdx.x; e < q; e += blockDim.x) theta[(size_t)v * q + e] = trial[(size_t)v * q + e];
-    if (threadIdx.x == 0) cost[v] = 0.5 * norms_t[v];
-  }
-}
-
 extern "C" int sbm_lm_accept(sbm_ctx* ctx, const int32_t* accept, int32_t V, int32_t M, int32_t q, const double* trial,
                              const double* r_trial, const double* J_trial, const double* norms_trial, double* theta,
                              double* r, double* J, double* cost) {
@@ -1929,68 +1397,11 @@ extern "C" int sbm_lm_accept(sbm_ctx* ctx, const int32_t* accept, int32_t V, int
 }
 
 // ---------------------------------------------------------------------------------------------
-// The Metropolis sampler's step on the device (project/ensembles.py, sampler='device'): scale-factor entropy of the
-// trial simulations, candidate move, acceptance.  Between sbm_mh_propose, sbm_residuals_batch, sbm_project_sf_entropy
-// and sbm_mh_accept no number goes through the host.
+// The Metropolis sampler's step on the device (kernels: sbm_sampler.hpp, sbm_sampling_axes.hpp): scale-factor entropy
+// of the trial simulations, candidate move, and the acceptance rules of its two algorithms -- Metropolis with fixed axes
+// (project/ensembles.py, sampler='device'), and Hastings with axes of the candidate density from the Hessian at every
+// chain's point (sampler='device_recalc').
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-// One workgroup of four wavefronts per vector; wavefront w takes the groups w, w + 4, ...  For a group the rows go along
-// the lanes (a = sum s^2 / sigma^2, b = sum s d / sigma^2 by a butterfly), then the panels of the quadrature rule
-// (sbm_sf_quadrature.hpp) do: lane l integrates panels l and l + 64 and the wavefront combines the 64 partial
-// log-sum-exps.  LDS: the G group values of the vector, summed in group order by one thread, so that the entropy does
-// not depend on which wavefront finished first.
-__global__ void __launch_bounds__(256) k_sf_entropy(const double* __restrict__ sims, int R, int G,
-                                                    const double* __restrict__ row_data, const double* __restrict__ row_sigma,
-                                                    const int32_t* __restrict__ row_sf, const double* __restrict__ sfg_mean,
-                                                    const double* __restrict__ sfg_sigma, double temperature,
-                                                    double* __restrict__ entropy, double* __restrict__ group_entropy) {
-  extern __shared__ double s_group[];   // [G]
-  const int v = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const double* sv = sims + (size_t)v * R;
-  for (int k = wave; k < G; k += 4) {
-    double a = 0.0, b = 0.0;
-    int bad = 0;
-    for (int r = lane; r < R; r += 64) {
-      const double s = sv[r];
-      bad |= !(fabs(s) <= 1.79769313486231570815e308);       // any row of the vector, scale factor or not
-      if (row_sf[r] == k) {
-        const double w = 1.0 / (row_sigma[r] * row_sigma[r]);
-        a = fma(s * s, w, a);
-        b = fma(s * row_data[r], w, b);
-      }
-    }
-    a = wave_sum(a);
-    b = wave_sum(b);
-    bad = __any(bad);
-    double alpha = 0.0, c = 0.0, val = -__builtin_inf();
-    if (!bad && sbm_sfq_params(a, b, sfg_mean[k], temperature, &alpha, &c)) {
-      sbm_sfq_plan q;
-      sbm_sfq_make_plan(alpha, c, sfg_sigma[k], &q);         // (the same on every lane)
-      double m = -__builtin_inf(), sum = 0.0;
-      sbm_sfq_add_panel(q, lane, &m, &sum);
-      sbm_sfq_add_panel(q, lane + 64, &m, &sum);
-      const double mw = wave_max(m);
-      const double tot = wave_sum(m > -__builtin_inf() ? sum * exp(m - mw) : 0.0);
-      val = mw + log(tot);                                    // (no panel at all: -inf + log 0 = -inf)
-    }
-    if (lane == 0) {
-      s_group[k] = val;
-      if (group_entropy) group_entropy[(size_t)v * G + k] = val;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double e = 0.0;
-    for (int k = 0; k < G; ++k) e += temperature * s_group[k];
-    entropy[v] = e == e ? e : -__builtin_inf();
-  }
-}
-
 extern "C" int sbm_project_sf_entropy(sbm_project* p, const double* sims, int32_t V, double temperature, double* entropy,
                                       double* group_entropy) {
   if (!p || !sims || !entropy) return sbm_fail(SBM_E_ARG, "sbm_project_sf_entropy: NULL argument");
@@ -2001,25 +1412,8 @@ extern "C" int sbm_project_sf_entropy(sbm_project* p, const double* sims, int32_
     return sbm_fail(SBM_E_ARG, "sbm_project_sf_entropy: scale factor entropy needs a log prior on every scale factor (group %d has none)",
                     p->sf_group_without_prior);
   if (V == 0) return 0;
-  SBM_HIP(hipSetDevice(p->model->ctx->device));
-  hipLaunchKernelGGL(k_sf_entropy, dim3(V), dim3(256), sizeof(double) * (size_t)p->G, p->model->ctx->stream, sims, p->R, p->G,
-                     p->row_data.p, p->row_sigma.p, p->row_sf.p, p->sfg_mean.p, p->sfg_sigma.p, temperature, entropy, group_entropy);
-  SBM_HIP(hipGetLastError());
-  return 0;
-}
-
-// trial = curr + samp z: one thread per (chain, component); samp is one [q][q] matrix or one per chain
-__global__ void __launch_bounds__(256) k_mh_propose(const double* __restrict__ curr, const double* __restrict__ samp, int per_chain,
-                                                    const double* __restrict__ z, int C, int q, double* __restrict__ trial) {
-  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (size_t)C * q) return;
-  const size_t c = idx / q;
-  const int i = (int)(idx % q);
-  const double* row = samp + (per_chain ? c * q * q : 0) + (size_t)i * q;
-  const double* zc = z + c * q;
-  double d = 0.0;
-  for (int j = 0; j < q; ++j) d = fma(row[j], zc[j], d);
-  trial[idx] = curr[idx] + d;
+  return launch_lds(p->model->ctx, k_sf_entropy, dim3(V), dim3(256), sizeof(double) * (size_t)p->G, sims, p->R, p->G, p->row_data.p,
+                    p->row_sigma.p, p->row_sf.p, p->sfg_mean.p, p->sfg_sigma.p, temperature, entropy, group_entropy);
 }
 
 extern "C" int sbm_mh_propose(sbm_ctx* ctx, const double* curr, const double* samp, int32_t per_chain, const double* z, int32_t C,
@@ -2034,35 +1428,6 @@ extern "C" int sbm_mh_propose(sbm_ctx* ctx, const double* curr, const double* sa
   return 0;
 }
 
-// One wavefront per chain: every lane reads the chain's scalars and takes the same decision, the lanes stride over the
-// q components, lane 0 writes the scalars.
-__global__ void __launch_bounds__(256) k_mh_accept(const double* __restrict__ norms_t, const int32_t* __restrict__ status_t,
-                                                   const double* __restrict__ entropy_t, const double* __restrict__ log_u,
-                                                   double temperature, int C, int q, const double* __restrict__ trial,
-                                                   double* __restrict__ curr, double* __restrict__ F_curr,
-                                                   int32_t* __restrict__ n_accepted, double* __restrict__ ens_slot,
-                                                   double* __restrict__ ens_F_slot) {
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (c >= C) return;
-  const double Fc = F_curr[c];
-  const double Ft = 0.5 * norms_t[c] - (entropy_t ? entropy_t[c] : 0.0);
-  const bool finite = fabs(Ft) <= 1.79769313486231570815e308;       // (false for NaN)
-  const bool acc = status_t[c] == 0 && finite && log_u[c] < -(Ft - Fc) / temperature;
-  for (int i = lane; i < q; i += 64) {
-    const size_t e = (size_t)c * q + i;
-    const double x = acc ? trial[e] : curr[e];
-    if (acc) curr[e] = x;
-    if (ens_slot) ens_slot[e] = x;
-  }
-  if (lane == 0) {
-    if (acc) {
-      F_curr[c] = Ft;
-      n_accepted[c] += 1;
-    }
-    if (ens_F_slot) ens_F_slot[c] = acc ? Ft : Fc;
-  }
-}
-
 extern "C" int sbm_mh_accept(sbm_ctx* ctx, const double* norms_trial, const int32_t* status_trial, const double* entropy_trial,
                              const double* log_u, double temperature, int32_t C, int32_t q, const double* trial, double* curr,
                              double* F_curr, int32_t* n_accepted, double* ens_slot, double* ens_F_slot) {
@@ -2071,17 +1436,13 @@ extern "C" int sbm_mh_accept(sbm_ctx* ctx, const double* norms_trial, const int3
   if (C < 0 || q <= 0) return sbm_fail(SBM_E_ARG, "sbm_mh_accept: bad sizes C=%d q=%d", C, q);
   if (!(temperature > 0.0)) return sbm_fail(SBM_E_ARG, "sbm_mh_accept: temperature must be positive");
   if (C == 0) return 0;
+  sbm_mh_args a{norms_trial, status_trial, entropy_trial, log_u, temperature, C, q, trial, curr, F_curr, n_accepted, ens_slot, ens_F_slot};
   SBM_HIP(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_mh_accept, dim3((C + 3) / 4), dim3(256), 0, ctx->stream, norms_trial, status_trial, entropy_trial, log_u,
-                     temperature, C, q, trial, curr, F_curr, n_accepted, ens_slot, ens_F_slot);
+  hipLaunchKernelGGL(k_mh_accept, dim3((C + 3) / 4), dim3(256), 0, ctx->stream, a);
   SBM_HIP(hipGetLastError());
   return 0;
 }
 
-// ---------------------------------------------------------------------------------------------
-// The sampler's second algorithm (project/ensembles.py, sampler='device_recalc'): axes of the candidate density from
-// the Hessian at every chain's point, and the Hastings rule (kernels: sbm_sampling_axes.hpp).
-// ---------------------------------------------------------------------------------------------
 extern "C" int sbm_sampling_axes(sbm_ctx* ctx, const double* J, const double* row_scale, const double* H, int32_t per_chain_H,
                                  int32_t C, int32_t M, int32_t q, double cutoff, double temperature, double step_scale,
                                  double* eig, double* V, double* s, double* samp, int32_t* status) {
@@ -2095,15 +1456,11 @@ extern "C" int sbm_sampling_axes(sbm_ctx* ctx, const double* J, const double* ro
   if (!(cutoff >= 0.0) || !(temperature > 0.0) || !(step_scale > 0.0))
     return sbm_fail(SBM_E_ARG, "sbm_sampling_axes: cutoff must be >= 0, temperature and step_scale positive");
   if (C == 0) return 0;
-  SBM_HIP(hipSetDevice(ctx->device));
   const size_t lds = sbm_axes_lds_bytes(q);
   if (lds > (size_t)lm_lds_limit(ctx))
     return sbm_fail(SBM_E_ARG, "sbm_sampling_axes: q = %d does not fit the %d KB of LDS of a workgroup", q, lm_lds_limit(ctx) / 1024);
   sbm_axes_args a{J, row_scale, H, per_chain_H, M, q, cutoff, temperature, step_scale, eig, V, s, samp, status};
-  if (lds > 64 * 1024) SBM_HIP(hipFuncSetAttribute((const void*)k_sampling_axes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_sampling_axes, dim3(C), dim3(256), lds, ctx->stream, a);
-  SBM_HIP(hipGetLastError());
-  return 0;
+  return launch_lds(ctx, k_sampling_axes, dim3(C), dim3(256), lds, a);
 }
 
 extern "C" int sbm_mh_accept_hastings(sbm_ctx* ctx, const double* norms_trial, const int32_t* status_trial,
@@ -2117,15 +1474,11 @@ extern "C" int sbm_mh_accept_hastings(sbm_ctx* ctx, const double* norms_trial, c
   if (C < 0 || q <= 0) return sbm_fail(SBM_E_ARG, "sbm_mh_accept_hastings: bad sizes C=%d q=%d", C, q);
   if (!(temperature > 0.0)) return sbm_fail(SBM_E_ARG, "sbm_mh_accept_hastings: temperature must be positive");
   if (C == 0) return 0;
-  SBM_HIP(hipSetDevice(ctx->device));
   const size_t lds = sizeof(double) * (size_t)q;
   if (lds > (size_t)lm_lds_limit(ctx)) return sbm_fail(SBM_E_ARG, "sbm_mh_accept_hastings: q = %d does not fit the LDS of a workgroup", q);
-  sbm_mh_hastings_args a{norms_trial, status_trial, entropy_trial, log_u, temperature, C, q, trial, curr, F_curr, n_accepted,
-                         ens_slot, ens_F_slot, V_curr, s_curr, samp_curr, V_trial, s_trial, samp_trial, axes_status_trial};
-  if (lds > 64 * 1024) SBM_HIP(hipFuncSetAttribute((const void*)k_mh_accept_hastings, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_mh_accept_hastings, dim3(C), dim3(256), lds, ctx->stream, a);
-  SBM_HIP(hipGetLastError());
-  return 0;
+  sbm_mh_hastings_args a{{norms_trial, status_trial, entropy_trial, log_u, temperature, C, q, trial, curr, F_curr, n_accepted,
+                          ens_slot, ens_F_slot}, V_curr, s_curr, samp_curr, V_trial, s_trial, samp_trial, axes_status_trial};
+  return launch_lds(ctx, k_mh_accept_hastings, dim3(C), dim3(256), lds, a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2167,8 +1520,6 @@ extern "C" int sbm_ensemble_stats(sbm_ctx* ctx, const double* values, const int3
   }
   const int threads = wide ? 1024 : 256;
   const size_t lds = sizeof(double) * ((size_t)C * (size_t)(C > 1 ? slots + 1 : slots) + (size_t)threads / 64);
-  if (lds > 64 * 1024)
-    SBM_HIP(hipFuncSetAttribute((const void*)k_ens_columns<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   sbm_ens_cols_args a;
   a.n_ptr = ctx->ens_n.p;
   a.L = L;
@@ -2186,12 +1537,10 @@ extern "C" int sbm_ensemble_stats(sbm_ctx* ctx, const double* values, const int3
     a.j0 = j0;
     a.n_cols = (int32_t)nc;
     const unsigned blocks = (unsigned)((nc + C - 1) / C);
-    if (wide)
-      hipLaunchKernelGGL(k_ens_columns<1024>, dim3(blocks), dim3(1024), lds, s, a, lv);
-    else
-      hipLaunchKernelGGL(k_ens_columns<256>, dim3(blocks), dim3(256), lds, s, a, lv);
+    if (int rc = wide ? launch_lds(ctx, k_ens_columns<1024>, dim3(blocks), dim3(1024), lds, a, lv)
+                      : launch_lds(ctx, k_ens_columns<256>, dim3(blocks), dim3(256), lds, a, lv))
+      return rc;
   }
-  SBM_HIP(hipGetLastError());
   return 0;
 }
 

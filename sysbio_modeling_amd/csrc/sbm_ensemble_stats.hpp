@@ -32,6 +32,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sbm_block_reduce.hpp"
+
 #define SBM_ENS_MAX_LEVELS 64           // quantile levels of one call (they travel as a kernel argument)
 #define SBM_ENS_PACK_SLOTS 2048         // slots of a workgroup that packs columns
 #define SBM_ENS_PACK_MAX_COLS 32
@@ -46,7 +48,7 @@ __global__ void __launch_bounds__(256) k_ens_valid(const double* __restrict__ va
   if (v >= V) return;
   const double* row = values + (size_t)v * (size_t)L;
   int bad = 0;
-  for (int64_t j = lane; j < L; j += 64) bad |= !(fabs(row[j]) <= 1.79769313486231570815e308);      // (true for NaN)
+  for (int64_t j = lane; j < L; j += 64) bad |= !is_finite(row[j]);
   bad = __any(bad);
   if (lane == 0) flag[v] = (!bad && (status == nullptr || status[v] == 0)) ? 1 : 0;
 }

@@ -1,7 +1,7 @@
-// sbm_sampling_axes.hpp -- kernels of sbm_sampling_axes and sbm_mh_accept_hastings (include/sbm.h): what the second
-// algorithm of the reference's sampler (project/Ensembles.py:153-157, 200-258) needs per chain and step besides the
-// integration -- the eigen-decomposition of the Gauss-Newton Hessian at the trial point with SloppyCell's clipping recipe
-// on top, and the Metropolis-Hastings rule with the candidate density at both ends of the move.
+// sbm_sampling_axes.hpp -- kernel of sbm_sampling_axes (include/sbm.h): what the second algorithm of the reference's
+// sampler (project/Ensembles.py:153-157, 200-258) needs per chain and step besides the integration and the
+// Metropolis-Hastings rule (sbm_sampler.hpp) -- the eigen-decomposition of the Gauss-Newton Hessian at the trial point
+// with SloppyCell's clipping recipe on top.
 //
 // k_sampling_axes: one 256-thread workgroup per chain, one launch for everything.
 //   1. A = H / 2.  From a Jacobian: row tiles of J (times row_scale) go through LDS -- the tile borrows the space of V,
@@ -21,15 +21,14 @@
 // LDS: A and V at leading dimension q + 1 -- the passes map consecutive lanes to consecutive columns, so the padding only
 // matters to the sign scan down a column -- plus 5 q doubles and 2 q ints: 153 600 bytes at q = SBM_SAMPLING_AXES_MAX_Q = 96.
 // No arrays in registers, no scratch.
-//
-// k_mh_accept_hastings: one workgroup per chain (there are q^2 axis entries to copy on acceptance); the two quadratic
-// forms are strided over the threads and summed in a fixed shape, so every thread takes the same decision.
 #ifndef SBM_SAMPLING_AXES_HPP
 #define SBM_SAMPLING_AXES_HPP
 
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <stdint.h>
+
+#include "sbm_block_reduce.hpp"
 
 #define SBM_AXES_MAX_SWEEPS 40
 
@@ -51,23 +50,6 @@ static inline size_t sbm_axes_lds_bytes(int q) {
   const size_t ld = (size_t)q + 1, np = ((size_t)q + 1) / 2;
   return sizeof(double) * (2 * (size_t)q * ld + 2 * np + 4 * (size_t)q) + sizeof(int) * (2 * np + (size_t)q);
 }
-
-__device__ __forceinline__ double sbm_axes_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// sum over the 256 threads, the same value on every thread; wavefront partials are added in wavefront order
-__device__ __forceinline__ double sbm_axes_block_sum(double v, double* red /*[4]*/) {
-  v = sbm_axes_wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-__device__ __forceinline__ bool sbm_axes_finite(double x) { return fabs(x) <= DBL_MAX; }      // (false for NaN)
 
 __global__ void __launch_bounds__(256) k_sampling_axes(sbm_axes_args a) {
   extern __shared__ __attribute__((aligned(16))) double ax_smem[];
@@ -101,7 +83,7 @@ __global__ void __launch_bounds__(256) k_sampling_axes(sbm_axes_args a) {
         double val = Jc[(size_t)(m0 + rr) * q + cc];
         if (a.row_scale) val *= a.row_scale[m0 + rr];
         T[rr * ld + cc] = val;
-        bad |= !sbm_axes_finite(val);
+        bad |= !is_finite(val);
       }
       __syncthreads();
       for (int e = tid; e < qq; e += 256) {
@@ -116,7 +98,7 @@ __global__ void __launch_bounds__(256) k_sampling_axes(sbm_axes_args a) {
       const int i = e / q, j = e - i * q;
       const double v = 0.5 * A[i * ld + j];
       A[i * ld + j] = v;
-      bad |= !sbm_axes_finite(v);
+      bad |= !is_finite(v);
     }
   } else {
     const double* Hc = a.H + (a.per_chain_H ? (size_t)c * qq : 0);
@@ -125,7 +107,7 @@ __global__ void __launch_bounds__(256) k_sampling_axes(sbm_axes_args a) {
       const double hij = Hc[(size_t)i * q + j], hji = Hc[(size_t)j * q + i];
       const double v = 0.5 * (0.5 * hij + 0.5 * hji);
       A[i * ld + j] = v;
-      bad |= !sbm_axes_finite(hij) || !sbm_axes_finite(v);
+      bad |= !is_finite(hij) || !is_finite(v);
     }
   }
   for (int e = tid; e < qq; e += 256) {
@@ -268,74 +250,6 @@ __global__ void __launch_bounds__(256) k_sampling_axes(sbm_axes_args a) {
 #else
   if (tid == 0) a.status[c] = 0;
 #endif
-}
-
-struct sbm_mh_hastings_args {
-  const double* norms_t;       // [C]
-  const int32_t* status_t;     // [C]
-  const double* entropy_t;     // [C] nullable
-  const double* log_u;         // [C]
-  double temperature;
-  int C, q;
-  const double* trial;         // [C][q]
-  double* curr;                // [C][q]    in / out
-  double* F_curr;              // [C]       in / out
-  int32_t* n_accepted;         // [C]       in / out
-  double* ens_slot;            // [C][q]    nullable
-  double* ens_F_slot;          // [C]       nullable
-  double *V_curr, *s_curr, *samp_curr;                     // [C][q][q], [C][q], [C][q][q]   in / out
-  const double *V_trial, *s_trial, *samp_trial;
-  const int32_t* axes_status_t;                            // [C]
-};
-
-__global__ void __launch_bounds__(256) k_mh_accept_hastings(sbm_mh_hastings_args a) {
-  extern __shared__ __attribute__((aligned(16))) double hs_d[];      // [q] the move
-  __shared__ double s_red[4];
-  const int c = blockIdx.x, tid = threadIdx.x, q = a.q;
-  const size_t o1 = (size_t)c * q, o2 = o1 * q;
-  for (int i = tid; i < q; i += 256) hs_d[i] = a.trial[o1 + i] - a.curr[o1 + i];
-  __syncthreads();
-  // log q(d; V, s) = -0.5 |V^T d / s|^2 - sum log s: forward with the current axes, back (-d) with the trial point's
-  double fwd = 0.0, back = 0.0;
-  for (int i = tid; i < q; i += 256) {
-    double uc = 0.0, ut = 0.0;
-    for (int j = 0; j < q; ++j) {
-      uc = fma(a.V_curr[o2 + (size_t)j * q + i], hs_d[j], uc);
-      ut = fma(a.V_trial[o2 + (size_t)j * q + i], -hs_d[j], ut);
-    }
-    const double sc = a.s_curr[o1 + i], st = a.s_trial[o1 + i];
-    uc /= sc;
-    ut /= st;
-    fwd += -0.5 * uc * uc - log(sc);
-    back += -0.5 * ut * ut - log(st);
-  }
-  fwd = sbm_axes_block_sum(fwd, s_red);
-  back = sbm_axes_block_sum(back, s_red);
-  const double Fc = a.F_curr[c];
-  const double Ft = 0.5 * a.norms_t[c] - (a.entropy_t ? a.entropy_t[c] : 0.0);
-  const bool acc = a.status_t[c] == 0 && a.axes_status_t[c] == 0 && sbm_axes_finite(Ft) &&
-                   a.log_u[c] < -(Ft - Fc) / a.temperature + back - fwd;
-  __syncthreads();                // every thread has read F_curr and the current axes
-  for (int i = tid; i < q; i += 256) {
-    const double x = acc ? a.trial[o1 + i] : a.curr[o1 + i];
-    if (acc) {
-      a.curr[o1 + i] = x;
-      a.s_curr[o1 + i] = a.s_trial[o1 + i];
-    }
-    if (a.ens_slot) a.ens_slot[o1 + i] = x;
-  }
-  if (acc)
-    for (int e = tid; e < q * q; e += 256) {
-      a.V_curr[o2 + e] = a.V_trial[o2 + e];
-      a.samp_curr[o2 + e] = a.samp_trial[o2 + e];
-    }
-  if (tid == 0) {
-    if (acc) {
-      a.F_curr[c] = Ft;
-      a.n_accepted[c] += 1;
-    }
-    if (a.ens_F_slot) a.ens_F_slot[c] = acc ? Ft : Fc;
-  }
 }
 
 #endif  // SBM_SAMPLING_AXES_HPP

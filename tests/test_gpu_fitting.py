@@ -174,6 +174,62 @@ def test_lm_trust_step_ex_clip_skip_scale_and_near_singular_systems():
     assert s2.tolist() == [0, 0]
 
 
+@pytest.mark.parametrize('V,M,q', [
+    (3, 1, 1),        # one row, one column: a single tile entry
+    (3, 33, 23),      # q (q + 1) / 2 = 276 > 256: some threads own two entries of the triangle, some one; a full tile + 1 row
+    (2, 100, 96),     # 74 KB of LDS: more than a kernel gets without asking (both kernels still stage 32 rows at a time)
+    (2, 260, 127),    # 16-row tiles in both kernels (32 rows and a 127 x 128 matrix are beyond the 160 KB of a workgroup)
+])
+def test_lm_step_and_trust_step_share_their_normal_equations(V, M, q):
+    """sbm_lm_step and sbm_lm_trust_step build J^T J, J^T r and the Cholesky factor with the same code: both against numpy at
+    the sizes where the ownership of the triangle, the row tiles and the launch change, and against each other -- without
+    damping (lambda = 0; a radius far beyond the Gauss-Newton step and no scaling from earlier calls) they return the same
+    step."""
+    import torch
+    from sysbio_modeling_amd import _lib
+    rng = np.random.default_rng(100 * q + M)
+    J = rng.standard_normal((V, M, q))
+    r = rng.standard_normal((V, M))
+    lam = np.array([0.3, 1e-2, 2.0])[:V]
+    gauss_newton = np.stack([np.linalg.lstsq(J[v], -r[v], rcond=None)[0] for v in range(V)])
+    col_norm = np.linalg.norm(J, axis=1)
+    radius = np.full(V, 1e6)
+    assert np.all(np.linalg.norm(col_norm * gauss_newton, axis=1) < 1e-3 * radius)      # these seeds: far inside
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()     # noqa: E731
+    Jd, rd = t(J), t(r)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device='cuda')     # noqa: E731
+    st = torch.empty((V,), dtype=torch.int32, device='cuda')
+    ctx = _lib.default_context()
+    p = _lib.dev_ptr
+
+    def lm_step(lam_v):
+        delta, pred, ld = new(V, q), new(V), t(lam_v)
+        _lib.check(ctx.lib.sbm_lm_step(ctx.handle, p(Jd), p(rd), p(ld), V, M, q, p(delta), p(pred), p(st)), 'sbm_lm_step')
+        torch.cuda.synchronize()
+        assert st.tolist() == [0] * V
+        return delta.cpu().numpy()
+
+    damped = lm_step(lam)
+    for v in range(V):
+        A, g = J[v].T @ J[v], J[v].T @ r[v]
+        ref = np.linalg.solve(A + lam[v] * np.diag(np.diag(A)), -g)
+        assert np.allclose(damped[v], ref, rtol=1e-9, atol=1e-12)
+    undamped = lm_step(np.zeros(V))
+
+    Dd, Ld = torch.zeros((V, q), dtype=torch.float64, device='cuda'), torch.zeros((V,), dtype=torch.float64, device='cuda')
+    delta, pred, dxn, Rd = new(V, q), new(V), new(V), t(radius)
+    _lib.check(ctx.lib.sbm_lm_trust_step(ctx.handle, p(Jd), p(rd), p(Dd), p(Rd), p(Ld), V, M, q, p(delta), p(pred), p(dxn),
+                                         p(st)), 'sbm_lm_trust_step')
+    torch.cuda.synchronize()
+    delta, D = delta.cpu().numpy(), Dd.cpu().numpy()
+    assert st.tolist() == [0] * V and Ld.tolist() == [0.0] * V
+    assert np.allclose(D, col_norm, rtol=1e-13)
+    for v in range(V):
+        A, g = J[v].T @ J[v], J[v].T @ r[v]
+        assert np.allclose(A @ delta[v], -g, rtol=1e-7, atol=1e-9 * np.abs(g).max())
+    assert np.allclose(delta, undamped, rtol=1e-9, atol=1e-12)
+
+
 def test_fused_trust_region_loop_equals_the_tensor_select_loop(gpu_models):
     """fit_batch(algorithm='trust_region') -- lmder's bookkeeping in sbm_lm_update / sbm_lm_accept, two launches per
     iteration -- against round 2's spelling of the same algorithm in tensor selects (algorithm='trust_region_torch'):
