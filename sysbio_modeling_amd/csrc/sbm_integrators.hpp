@@ -62,6 +62,20 @@ __device__ __forceinline__ double sbm_pick(int scol, int c, double v, double oth
 #define SBM_PICK(scol, c, v, otherwise) sbm_pick(scol, c, v, otherwise)
 __device__ __forceinline__ double sbm_sel(bool c, double a, double b) { return c ? a : b; }
 #define SBM_SEL(c, a, b) sbm_sel(c, a, b)
+// max(|a|, |b|) of the DOPRI45 error norm's scale in ONE v_max_f64 with the absolute values as source modifiers.
+// fmax(fabs(a), fabs(b)) compiles to two: where an operand is carried round the step loop the compiler first quiets a
+// possible signalling NaN with v_max_f64 x, |a|, |a|.  With one NaN operand the instruction returns the other operand
+// (a signalling NaN it returns quieted: IEEE mode is on in compute kernels); either way the error estimate of such an
+// element is NaN itself and the step is rejected, which is all the controller needs.
+__device__ __forceinline__ double sbm_max_abs(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double m;
+  asm("v_max_f64 %0, |%1|, |%2|" : "=v"(m) : "v"(a), "v"(b));
+  return m;
+#else
+  return fmax(fabs(a), fabs(b));
+#endif
+}
 // (col == c ? v : otherwise) for col = lane + 64 * chunk (chunk wave-uniform) and a literal c: the lane mask comes from
 // scalar instructions (the inverse of a ballot: s_mov / s_cselect of the literal), the select is the v_cndmask pair alone
 __device__ __forceinline__ double sbm_pick_col(int col, int c, double v, double otherwise) {
@@ -534,7 +548,7 @@ __device__ __forceinline__ SbmTrajOut sbm_dopri45(const Sys& sys, double (&z)[Sy
       float xsum = 0.f;
       auto err_ratio = [&](int c, int i) {
         const double e = fma(E7, k1[c][i], k4[c][i]);
-        const double sc = fma(rtol, fmax(fabs(z[c][i]), fabs(zt[c][i])), atol);
+        const double sc = fma(rtol, sbm_max_abs(z[c][i], zt[c][i]), atol);
         return (float)e * __builtin_amdgcn_rcpf((float)sc);
       };
 #pragma unroll

@@ -139,8 +139,9 @@ class ModelSpec:
 class Derived:
     """f, nnz(J_y), nnz(J_p) after joint CSE."""
 
-    def __init__(self, spec: ModelSpec):
+    def __init__(self, spec: ModelSpec, class_align: bool = True):
         self.spec = spec
+        self.class_align = class_align
         params = OrderedDict((p, 'fixed' if p in spec.fixed else Symbol(p)) for p in spec.params)
         jy, jp = sympy_tools.derive_sparse_jacobians(spec.equations, params)
         self.jy = jy  # (row, col, expr)
@@ -170,6 +171,31 @@ class Derived:
         for e, (r, c, _) in enumerate(jp):
             self.jp_rows[r].append((e, c))
         self._order_slots_by_structure()
+        self._align_class_slots()
+
+    def _align_class_slots(self):
+        """Which slot of ``class_dispatch`` each operand and output of a row takes.  The row-lane classes number them in
+        order of first appearance, so two kinetic forms put the same role (the saturating state, the rate constant, the
+        diagonal entry) into different slots and every output is a select between class bodies that differ for no other
+        reason: ``emit_rowlane.choose_alignment`` picks, per class, positions that make the bodies agree (``align``;
+        None: first appearance).  The output positions are applied HERE, to the order of ``jy_rows[i]`` / ``jp_rows[i]``
+        -- the slot of an entry is its index in its row, and every table of every row kernel is printed from these two
+        lists; the operand positions are applied by ``emit_rowlane.find_classes``.  ``jy_base`` / ``jp_base`` keep the
+        rows as they were: the classes are found on them, and the sums over a row's J_y entries (apply_col, eval_col,
+        apply_rowlane, apply_lds, the Python model) keep their order of summation."""
+        from . import emit_rowlane
+        self.align = None
+        self.jy_base = [list(r) for r in self.jy_rows]
+        self.jp_base = [list(r) for r in self.jp_rows]
+        if self.class_align:
+            self.align = emit_rowlane.choose_alignment(
+                self.spec, self, lambda smap: _ExprPrinter(smap, rcp="SBM_RCP(%s)", lang='hip'))
+        if self.align is not None:
+            classes, row_info = emit_rowlane.find_classes(self.spec, self)
+            for i, r in enumerate(row_info):
+                c = classes[r['cls']]
+                self.jy_rows[i] = [ec for _, ec in sorted(zip(c['jy_slot'], self.jy_base[i]))]
+                self.jp_rows[i] = [ec for _, ec in sorted(zip(c['jp_slot'], self.jp_base[i]))]
 
     def _order_slots_by_structure(self):
         """The row-lane class finder (emit_rowlane.find_classes) compares the expression bundles of rows slot by slot,
@@ -323,7 +349,7 @@ def emit_python(spec: ModelSpec, derived: Derived = None) -> str:
         L.append(pad + "jp_%d = %s" % (e_idx, pr.doprint(e)))
     for i in range(n):
         for j in range(k):
-            terms = ["jy_%d*y[%d]" % (e_idx, n + c * k + j) for e_idx, c in d.jy_rows[i]]
+            terms = ["jy_%d*y[%d]" % (e_idx, n + c * k + j) for e_idx, c in d.jy_base[i]]
             terms += ["jp_%d" % e_idx for e_idx, c in d.jp_rows[i] if c == j]
             L.append(pad + "yout[%d] = (%s)" % (n + i * k + j, " + ".join(terms) if terms else "0.0"))
     L.append("")
@@ -462,7 +488,7 @@ def emit_c(spec: ModelSpec, derived: Derived = None) -> str:
 # ----------------------------------------------------------------------------
 # HIP device struct
 # ----------------------------------------------------------------------------
-def emit_hip(spec: ModelSpec, derived: Derived = None, class_hoist: bool = True) -> str:
+def emit_hip(spec: ModelSpec, derived: Derived = None, class_hoist: bool = True, class_align: bool = None) -> str:
     """Header defining ``struct SbmModel`` consumed by csrc/sbm_integrators.hpp.
 
     ``eval_f``   : state RHS only (state-only kernels, one trajectory per lane).
@@ -473,8 +499,19 @@ def emit_hip(spec: ModelSpec, derived: Derived = None, class_hoist: bool = True)
                    in VGPRs.
     ``class_hoist``: evaluate an expensive operation that several row-lane classes have in common once, on
                    selected operands (emit_rowlane.py); False prints every class body in full, as a reference.
+    ``class_align``: let the row-lane classes agree on which slot holds which operand and output
+                   (``Derived._align_class_slots``); False keeps every class's first-appearance numbering, as a
+                   reference.  The choice does not depend on ``class_hoist``.  Default: what ``derived`` was made
+                   with (True without one); a ``derived`` made with the other setting is an error.  Where an
+                   alignment is chosen, a product that is a whole output of a class and a factor group of another
+                   of its outputs is also printed once, as a temporary (``emit_rowlane._share_products``): the
+                   aligned form is costed and printed with it, the unaligned form never has it.
     """
-    d = derived or Derived(spec)
+    if derived is None:
+        derived = Derived(spec, class_align=True if class_align is None else class_align)
+    elif class_align is not None and derived.class_align != class_align:
+        raise ValueError("emit_hip: derived was made with class_align=%s" % derived.class_align)
+    d = derived
     n, k = spec.n_vars, spec.n_sens
     pr = _ExprPrinter(_symbol_map(spec), rcp="SBM_RCP(%s)", lang='hip')
     nnz_y, nnz_p = max(len(d.jy), 1), max(len(d.jp), 1)
@@ -529,10 +566,10 @@ def emit_hip(spec: ModelSpec, derived: Derived = None, class_hoist: bool = True)
           "                                                   int scol, const double (&z)[NV], double (&dz)[NV]) {"]
     for i in range(n):
         sel = "0.0"
-        for e_idx, c in reversed(d.jp_rows[i]):
+        for e_idx, c in reversed(d.jp_base[i]):
             sel = "SBM_PICK(scol, %d, jp[%d], %s)" % (c, e_idx, sel)
         expr = sel
-        for e_idx, c in d.jy_rows[i]:
+        for e_idx, c in d.jy_base[i]:
             expr = "fma(jy[%d], z[%d], %s)" % (e_idx, c, expr)
         L.append("    dz[%d] = %s;" % (i, expr))
     L += ["  }", ""]
@@ -555,7 +592,7 @@ def emit_hip(spec: ModelSpec, derived: Derived = None, class_hoist: bool = True)
                 out.append(s)
 
     for i in range(n):
-        exprs = [d.f_red[i]] + [d.jy_red[e] for e, _ in d.jy_rows[i]] + [d.jp_red[e] for e, _ in d.jp_rows[i]]
+        exprs = [d.f_red[i]] + [d.jy_red[e] for e, _ in d.jy_base[i]] + [d.jp_red[e] for e, _ in d.jp_base[i]]
         todo = []
         for e in exprs:
             need(e, todo)
@@ -563,10 +600,10 @@ def emit_hip(spec: ModelSpec, derived: Derived = None, class_hoist: bool = True)
             L.append("    const double %s = %s;" % (s, pr.doprint(temp_expr[s])))
             emitted.add(s)
         sel = "0.0"
-        for e_idx, c in reversed(d.jp_rows[i]):
+        for e_idx, c in reversed(d.jp_base[i]):
             sel = "SBM_PICK(scol, %d, %s, %s)" % (c, pr.doprint(d.jp_red[e_idx]), sel)
         expr = sel
-        for e_idx, c in d.jy_rows[i]:
+        for e_idx, c in d.jy_base[i]:
             expr = "fma(%s, z[%d], %s)" % (pr.doprint(d.jy_red[e_idx]), c, expr)
         L.append("    dz[%d] = SBM_SEL(state_lane, %s, %s);" % (i, pr.doprint(d.f_red[i]), expr))
     L += ["  }", ""]

@@ -42,45 +42,89 @@ def _canonical(bundle, var_index, par_index):
     return canon, ys, ps
 
 
-def find_classes(spec, d):
-    """Group rows by the structure of (f_i, J_y entries of the row, J_p entries of the row)."""
+def find_classes(spec, d, align='derived'):
+    """Group rows by the structure of (f_i, J_y entries of the row, J_p entries of the row).
+
+    A class numbers its operands and outputs in order of first appearance, so two kinetic forms put the same role into
+    different slots and ``class_dispatch`` selects between them for nothing.  ``align`` (default: what ``d`` chose,
+    ``choose_alignment``) gives per class the POSITION of each of its state / parameter operands and J_y / J_p outputs:
+    ``align[ci] = dict(ys=[...], ps=[...], jy=[...], jp=[...])``, entry k = the slot of the class's k-th operand or
+    output in the first-appearance numbering.  Operand positions need not be dense: a class with fewer operands than
+    another may leave any of their slots unused.  Output positions are a permutation of the class's own: the slot of
+    an entry stays its index in d.jy_rows[i] / d.jp_rows[i].  None: the first-appearance numbering itself.
+
+    Returns (classes, row_info).  A class: canon (f, the J_y entries, the J_p entries in the order of d.jy_base /
+    d.jp_base -- the rows before alignment --, symbols YS_<slot> / PS_<slot>), rows, ys_slot / ps_slot / jy_slot /
+    jp_slot.  A row: cls, ys / ps =
+    state / parameter index per slot (None: a slot the row's class does not use)."""
     var_index = {v: i for i, v in enumerate(spec.variables)}
     par_index = {p: i for i, p in enumerate(spec.params)}
     classes = OrderedDict()   # key -> dict(canon, rows=[...])
     row_info = []
+    jy_rows, jp_rows = getattr(d, 'jy_base', d.jy_rows), getattr(d, 'jp_base', d.jp_rows)
     for i in range(spec.n_vars):
-        bundle = [d.f_c[i]] + [d.jy_c[e] for e, _ in d.jy_rows[i]] + [d.jp_c[e] for e, _ in d.jp_rows[i]]
+        bundle = [d.f_c[i]] + [d.jy_c[e] for e, _ in jy_rows[i]] + [d.jp_c[e] for e, _ in jp_rows[i]]
         canon, ys, ps = _canonical(bundle, var_index, par_index)
-        key = (sympy.srepr(canon), len(d.jy_rows[i]), len(d.jp_rows[i]))
+        key = (sympy.srepr(canon), len(jy_rows[i]), len(jp_rows[i]))
         if key not in classes:
-            classes[key] = dict(canon=canon, rows=[], n_jy=len(d.jy_rows[i]), n_jp=len(d.jp_rows[i]),
+            classes[key] = dict(canon=canon, rows=[], n_jy=len(jy_rows[i]), n_jp=len(jp_rows[i]),
                                 n_ys=len(ys), n_ps=len(ps))
         classes[key]['rows'].append(i)
         row_info.append(dict(cls=list(classes.keys()).index(key), ys=ys, ps=ps))
-    return list(classes.values()), row_info
+    classes = list(classes.values())
+    if align == 'derived':
+        align = getattr(d, 'align', None)
+    _place(classes, align)
+    if align is not None:
+        for r in row_info:
+            c = classes[r['cls']]
+            for kind in ('ys', 'ps'):
+                at = [None] * (max(c[kind + '_slot'] + [-1]) + 1)
+                for k, s in enumerate(c[kind + '_slot']):
+                    at[s] = r[kind][k]
+                r[kind] = at
+    return classes, row_info
+
+
+def _place(classes, align):
+    """give the classes (first-appearance numbering) the slot positions of ``align``"""
+    for ci, c in enumerate(classes):
+        a = align[ci] if align is not None else dict(ys=range(c['n_ys']), ps=range(c['n_ps']), jy=range(c['n_jy']),
+                                                     jp=range(c['n_jp']))
+        for kind in ('ys', 'ps', 'jy', 'jp'):
+            c[kind + '_slot'] = list(a[kind])
+            assert len(c[kind + '_slot']) == c['n_' + kind] == len(set(c[kind + '_slot']))
+        if align is not None:
+            rename = {Symbol('YS_%d' % k): Symbol('YS_%d' % s) for k, s in enumerate(c['ys_slot'])}
+            rename.update({Symbol('PS_%d' % k): Symbol('PS_%d' % s) for k, s in enumerate(c['ps_slot'])})
+            c['canon'] = tuple(e.xreplace(rename) for e in c['canon'])
+
+
+def _n_slots(classes, kind):
+    return max([s + 1 for c in classes for s in c[kind + '_slot']] + [1])
 
 
 def emit_rowlane_tables(spec, d, printer_factory):
     """Namespace-scope ``__constant__`` tables + sizes; returns (lines, meta)."""
     classes, row_info = find_classes(spec, d)
     n = spec.n_vars
-    max_ys = max([c['n_ys'] for c in classes] + [1])
-    max_ps = max([c['n_ps'] for c in classes] + [1])
-    max_jy = max([c['n_jy'] for c in classes] + [1])
-    max_jp = max([c['n_jp'] for c in classes] + [1])
+    max_ys, max_ps, max_jy, max_jp = (_n_slots(classes, kind) for kind in ('ys', 'ps', 'jy', 'jp'))
     tag = "SBM_RL"
 
     def table(name, rows_of_slots):
         flat = ", ".join(str(v) for slot in rows_of_slots for v in slot)
         return "__constant__ short %s_%s[%d] = {%s};" % (tag, name, len(rows_of_slots) * n, flat)
 
-    ys_t = [[(row_info[i]['ys'][s] if s < len(row_info[i]['ys']) else 0) for i in range(n)] for s in range(max_ys)]
-    ps_t = [[(row_info[i]['ps'][s] if s < len(row_info[i]['ps']) else 0) for i in range(n)] for s in range(max_ps)]
+    def operand(i, kind, s):
+        at = row_info[i][kind]
+        return at[s] if s < len(at) and at[s] is not None else 0     # (an unused slot reads element 0: never used)
+
+    ys_t = [[operand(i, 'ys', s) for i in range(n)] for s in range(max_ys)]
+    ps_t = [[operand(i, 'ps', s) for i in range(n)] for s in range(max_ps)]
     nj = max(len(d.jy), 1)
     jy_t = [[(d.jy_rows[i][s][0] if s < len(d.jy_rows[i]) else nj) for i in range(n)] for s in range(max_jy)]
     # position in the additive matrix A[NV][64] (+ one spare slot at NV*64 for unused outputs)
-    jp_t = [[(i * 64 + d.jp_rows[i][s][1] if s < len(d.jp_rows[i]) else n * 64) for i in range(n)]
-            for s in range(max_jp)]
+    jp_t = [[(i * 64 + d.jp_rows[i][s][1] if s < len(d.jp_rows[i]) else n * 64) for i in range(n)] for s in range(max_jp)]
     # the column alone (-1: unused slot), for kernels that cut the columns into chunks (any number of columns)
     jpc_t = [[(d.jp_rows[i][s][1] if s < len(d.jp_rows[i]) else -1) for i in range(n)] for s in range(max_jp)]
     # the column of each J_y slot (-1: unused), for the kernel that hands J_y to the matrix cores as a dense tile
@@ -89,7 +133,8 @@ def emit_rowlane_tables(spec, d, printer_factory):
          "__constant__ short %s_CLASS[%d] = {%s};" % (tag, n, ", ".join(str(r['cls']) for r in row_info)),
          table("YS", ys_t), table("PS", ps_t), table("JYOUT", jy_t), table("APOS", jp_t), table("JPCOL", jpc_t),
          table("JYCOL", jyc_t), ""]
-    meta = dict(classes=classes, max_ys=max_ys, max_ps=max_ps, max_jy=max_jy, max_jp=max_jp)
+    meta = dict(classes=classes, max_ys=max_ys, max_ps=max_ps, max_jy=max_jy, max_jp=max_jp,
+                share_products=getattr(d, 'align', None) is not None)
     return L, meta
 
 
@@ -121,6 +166,8 @@ def _tree_cost(node):
     if kind is None:
         return 0
     n = int(node.exp) - 1 if node.is_Pow and kind == 'mul' else max(len(node.args) - 1, 1)
+    if node.is_Mul and node.args[0] == -1:
+        n -= 1           # (a sign is a source modifier of the instruction that uses the product)
     return _OP_COST[kind] * n + sum(_tree_cost(a) for a in node.args)
 
 
@@ -128,7 +175,8 @@ def _plan_hoist(per_class, pr):
     """Operations that several classes have in common, to be evaluated ONCE on selected operands.
 
     Every class body is evaluated on every lane (class_dispatch below), so an operation that occurs in k classes costs k
-    times what a lane needs.  Where the classes' subtrees under an expensive root (reciprocal, sqrt, exp, log, pow)
+    times what a lane needs.  Where the classes' subtrees under one root (reciprocal, sqrt, exp, log, pow; a sum or a
+    product as well -- with the classes' slots aligned, choose_alignment, few of their operands differ)
     print to the SAME TEXT up to the operands at the leaves -- ys[.], ps[.], CSE temporaries, earlier shared values --
     the text is emitted once with each differing leaf replaced by a select chain on the class:
     op(sel(c, a, b)) and sel(c, op(a), op(b)) are the same value in every lane, and because the shared statement IS
@@ -164,10 +212,12 @@ def _plan_hoist(per_class, pr):
     def printed(ci, node):
         """text of ``node`` as class ci prints it, values shared so far by name; -> (shape, leaves)"""
         # a temporary that is a PRODUCT enters the shared text as its definition, not by name: where it feeds a sum the
-        # compiler contracts the two into one FMA, which it could not do through a select of two finished products
+        # compiler contracts the two into one FMA, which it could not do through a select of two finished products.
+        # (Under a cheap root -- a sum, a product -- it stays a name: there the temporary IS the operand the classes
+        # differ in, and the select of two finished values is what the sharing is for.)
         pr.shared = {k: v for k, v in shared[ci].items() if k != node}
         for (sym, _), e in zip(per_class[ci][0], exprs[ci]):
-            if _op_kind(e) == 'mul':
+            if _op_kind(e) == 'mul' and _op_kind(node) not in ('add', 'mul'):
                 pr.shared[sym] = "(%s)" % pr._print(e)
         text = pr._print(node)
         return _LEAF.sub('@', text), _LEAF.findall(text)
@@ -190,7 +240,7 @@ def _plan_hoist(per_class, pr):
                     if node in shared[ci]:
                         walk.skip()
                         continue
-                    if node in seen or _op_kind(node) in (None, 'add', 'mul'):
+                    if node in seen or _op_kind(node) is None or _tree_cost(node) == 0:
                         continue
                     seen.add(node)
                     shape, leaves = printed(ci, node)
@@ -251,34 +301,143 @@ def _sel_template(h):
     return "".join(out)
 
 
-def emit_rowlane_members(spec, d, meta, make_printer, hoist=True):
-    """Member functions of ``struct SbmModel`` for the row-lane kernel.  ``hoist=False``: every class body in full
-    (the reference form the shared one is checked against, tests/test_class_hoist.py)."""
-    n = spec.n_vars
-    classes = meta['classes']
-    L = ["  // ---- row-lane form (sbm_sens_rowlane_kernel) ----",
-         "  static constexpr int RL_NCLASS = %d;" % len(classes),
-         "  static constexpr int RL_MAXYS = %d, RL_MAXPS = %d, RL_MAXJY = %d, RL_MAXJP = %d;"
-         % (meta['max_ys'], meta['max_ps'], meta['max_jy'], meta['max_jp']),
-         "  static constexpr int RL_LARGEST_CLASS = %d;  // rows evaluated side by side" %
-         max(len(c['rows']) for c in classes),
-         "  // table accessors (the tables are namespace-scope __constant__ arrays above)",
-         "  __device__ __forceinline__ static int rl_class(int row) { return SBM_RL_CLASS[row]; }",
-         "  __device__ __forceinline__ static int rl_ys(int slot, int row) { return SBM_RL_YS[slot * NV + row]; }",
-         "  __device__ __forceinline__ static int rl_ps(int slot, int row) { return SBM_RL_PS[slot * NV + row]; }",
-         "  __device__ __forceinline__ static int rl_jyout(int slot, int row) { return SBM_RL_JYOUT[slot * NV + row]; }",
-         "  __device__ __forceinline__ static int rl_apos(int slot, int row) { return SBM_RL_APOS[slot * NV + row]; }",
-         "  __device__ __forceinline__ static int rl_jpcol(int slot, int row) { return SBM_RL_JPCOL[slot * NV + row]; }",
-         "  __device__ __forceinline__ static int rl_jycol(int slot, int row) { return SBM_RL_JYCOL[slot * NV + row]; }",
-         "  // one class body per distinct kinetic form; lane = row, operands per lane",
-         "  __device__ __forceinline__ static void class_dispatch(int cls, double t, const double (&ys)[RL_MAXYS],",
-         "                                                        const double (&ps)[RL_MAXPS], double& f,",
-         "                                                        double (&jy)[RL_MAXJY], double (&jp)[RL_MAXJP]) {",
-         "    (void)t; (void)ys; (void)ps;"]
+def _share_products(repl, red, prefix):
+    """A product that is a whole output of the class and also a group of factors of another output (a rate term
+    y/(K + y) is d f / d Vmax, and f holds Vmax times it) is evaluated once, as a temporary: the other classes then meet
+    ONE operand where this class has the product, and the sum around it can be shared (_plan_hoist)."""
+    repl, red = list(repl), list(red)
+    n_temp = len(repl)
+    for e in list(red):
+        if not (e.is_Mul and len(e.args) >= 2 and not e.args[0].is_Number):
+            continue
+        factors = set(e.args)
+
+        def holds(m):
+            return m.is_Mul and factors < set(m.args)
+        if not any(x.has(e) or any(holds(m) for m in sympy.preorder_traversal(x)) for x in red if x != e):
+            continue
+        sym = Symbol('%s%d' % (prefix, n_temp))
+        n_temp += 1
+        repl.append((sym, e))
+        red = [sym if x == e else x.replace(holds, lambda m: sympy.Mul(sym, *[a for a in m.args if a not in factors]))
+               for x in red]
+    return repl, red
+
+
+_CALL = re.compile(r'(?<![A-Za-z0-9_])([A-Za-z_][A-Za-z0-9_]*)\(')
+
+
+def _text_cost(lines):
+    """static cost of printed statements on the scale of _OP_COST / _SEL_COST"""
+    cost = 0
+    for ln in lines:
+        if '=' not in ln or ln.lstrip().startswith('//'):
+            continue
+        rhs = ln.split('=', 1)[1].split(';')[0]
+        if rhs.lstrip().startswith('(cls =='):
+            continue
+        for name in _CALL.findall(rhs):
+            cost += {'SBM_RCP': _OP_COST['rcp'], 'SBM_SEL': _SEL_COST, 'sqrt': _OP_COST['sqrt'], 'exp': _OP_COST['exp'],
+                     'log': _OP_COST['log'], 'pow': _OP_COST['pow']}.get(name, _OP_COST['call'])
+        cost += rhs.count('*') * _OP_COST['mul'] + (rhs.count(' + ') + rhs.count(' - ')) * _OP_COST['add']
+    return cost
+
+
+_MAX_CANDIDATES = 600     # all combinations up to here ...
+_MAX_GREEDY = 300         # ... beyond it, this many two-class bodies
+
+
+def choose_alignment(spec, d, make_printer):
+    """Slot positions per class (the ``align`` of find_classes) that make ``class_dispatch`` cheapest, or None when no
+    choice beats the first-appearance numbering (ties go to it: such a model prints as it always did).
+
+    The class with the most slots keeps its numbering.  For every other class the candidates are the placements of its
+    state operands and of its parameter operands among the slots of the widest class of each kind (a class with fewer
+    may leave any of them unused) and the permutations of its J_y outputs and of its J_p outputs.  Each candidate is
+    PRINTED -- with the sharing of _plan_hoist, whatever ``class_hoist`` the caller prints with, and with
+    _share_products -- and costed by _text_cost.  All combinations of all classes when there are at most
+    _MAX_CANDIDATES of them.  Otherwise greedy, one pass: each class against the reference class alone (a two-class
+    body prints in milliseconds whatever the number of classes) -- all combinations of the class where they are few,
+    because roles move together (the saturating state, its rate constant and the entry they make), else one slot kind
+    at a time -- until _MAX_GREEDY bodies have been printed.  Candidates are enumerated in lexicographic order and only
+    a strictly lower cost replaces the incumbent: deterministic."""
+    import math
+    from itertools import islice, permutations, product, repeat
+    base, _ = find_classes(spec, d, align=None)
+    if len(base) < 2:
+        return None
+    kinds = ('ys', 'ps', 'jy', 'jp')
+    width = {k: max(c['n_' + k] for c in base) for k in kinds}
+    n_slots = {k: max(width[k], 1) for k in kinds}
+    ref = max(range(len(base)), key=lambda ci: (sum(base[ci]['n_' + k] for k in kinds), -ci))
+    others = [ci for ci in range(len(base)) if ci != ref]
+    identity = [{k: tuple(range(c['n_' + k])) for k in kinds} for c in base]
+    memo = {}            # (the CSE of a class depends on its operand positions alone)
+
+    def cost(align, only=None):
+        classes = [dict(c) for c in base]
+        _place(classes, align)
+        if only is not None:
+            classes = [classes[ci] for ci in sorted(only)]
+        return _text_cost(_dispatch_body(classes, n_slots, make_printer, hoist=True, share_products=True, memo=memo))
+
+    # (candidates are counted arithmetically and taken lazily: a row with n entries has n! orders of them)
+    def placements(ci, k):
+        n_own = base[ci]['n_' + k]
+        return permutations(range(width[k] if k in ('ys', 'ps') else n_own), n_own)
+
+    def n_placements(ci, k):
+        n_own = base[ci]['n_' + k]
+        return math.perm(width[k] if k in ('ys', 'ps') else n_own, n_own)
+
+    def combos(ci):
+        return (dict(zip(kinds, combo)) for combo in product(*[placements(ci, k) for k in kinds]))
+
+    def n_combos(ci):
+        return math.prod(n_placements(ci, k) for k in kinds)
+
+    _place(base, None)
+    plain = _text_cost(_dispatch_body(base, n_slots, make_printer, hoist=True, share_products=False))
+    n_all = 1
+    for ci in others:
+        n_all = min(n_all * n_combos(ci), _MAX_CANDIDATES + 1)
+    if n_all <= _MAX_CANDIDATES:
+        best, best_cost = identity, cost(identity)
+        for choice in product(*[combos(ci) for ci in others]):
+            cand = list(identity)
+            for ci, a in zip(others, choice):
+                cand[ci] = a
+            c = cost(cand) if cand != identity else best_cost
+            if c < best_cost:
+                best, best_cost = cand, c
+        return best if best_cost < plain else None
+    best = list(identity)
+    for ci in others:
+        pair_cost = cost(best, only=(ref, ci))
+        if n_combos(ci) <= _MAX_GREEDY // 4:
+            rounds = [combos(ci)]
+        else:
+            rounds = [zip(repeat(k), placements(ci, k)) for k in kinds]
+        share = max(_MAX_GREEDY // (len(others) * len(rounds)), 1)       # (of the budget, for this round of this class)
+        for trials in rounds:
+            for a in islice(trials, share):
+                if isinstance(a, tuple):                  # (one kind moves, the others stay where the class has them)
+                    a = dict(best[ci], **{a[0]: a[1]})
+                if a == best[ci]:
+                    continue
+                c = cost(best[:ci] + [a] + best[ci + 1:], only=(ref, ci))
+                if c < pair_cost:
+                    best[ci], pair_cost = a, c
+    return best if cost(best) < plain else None
+
+
+def _dispatch_body(classes, n_slots, make_printer, hoist=True, share_products=False, memo=None):
+    """The statements of ``class_dispatch``.  ``share_products``: a product that is a whole output of a class and also a
+    group of factors of another of its outputs becomes a temporary of the class (``_share_products``)."""
     smap = {'t': 't'}
-    for s in range(meta['max_ys']):
+    for s in range(n_slots['ys']):
         smap['YS_%d' % s] = 'ys[%d]' % s
-    for s in range(meta['max_ps']):
+    for s in range(n_slots['ps']):
         smap['PS_%d' % s] = 'ps[%d]' % s
     pr = make_printer(smap)
     # Branch-free: every class body is evaluated on every lane (a divergent if/else chain would
@@ -287,12 +446,22 @@ def emit_rowlane_members(spec, d, meta, make_printer, hoist=True):
     # because other lanes read these registers with v_readlane.  The LAST class is the default of
     # the select chain (n-1 selects per output instead of n): lanes without a row (cls = -1) end up
     # with its values, which the kernels discard (spare LDS slots) or zero (f).
+    L = []
     last = len(classes) - 1
     for ci in range(last):
         L.append("    const bool is%d = (cls == %d);" % (ci, ci))
     is_last_at = len(L)   # (the last class is the default of the output chains; a shared operand may still select on it)
-    per_class = [cse(list(c['canon']), symbols=sympy.numbered_symbols('c%d_x' % ci), optimizations='basic')
-                 for ci, c in enumerate(classes)]
+    def class_cse(ci, canon):
+        key = (ci, canon, share_products)
+        if memo is not None and key in memo:
+            return memo[key]
+        repl, red = cse(list(canon), symbols=sympy.numbered_symbols('c%d_x' % ci), optimizations='basic')
+        if share_products:
+            repl, red = _share_products(repl, red, 'c%d_x' % ci)
+        if memo is not None:
+            memo[key] = (repl, red)
+        return repl, red
+    per_class = [class_cse(ci, c['canon']) for ci, c in enumerate(classes)]
     shared, hoisted = _plan_hoist(per_class, pr) if hoist and len(classes) > 1 else ([{} for _ in classes], [])
     # statements by name: the classes' CSE temporaries in their own order, a shared operation right before its first
     # use -- with the temporaries of OTHER classes that feed it pulled ahead of it
@@ -329,24 +498,56 @@ def emit_rowlane_members(spec, d, meta, make_printer, hoist=True):
         L.insert(is_last_at, "    const bool is%d = (cls == %d);" % (last, last))
 
     def chain(kind, k):
-        """value of output (kind, k): the last class's expression (or 0), overridden class by class"""
+        """value of output (kind, k): the last class's expression (or 0), overridden class by class; a text all classes
+        agree on is the value as it stands"""
         def of(ci):
             c = classes[ci]
             if kind == 'f':
                 return bodies[ci][0]
             if kind == 'jy':
-                return bodies[ci][1 + k] if k < c['n_jy'] else "0.0"
-            return bodies[ci][1 + c['n_jy'] + k] if k < c['n_jp'] else "0.0"
+                return bodies[ci][1 + c['jy_slot'].index(k)] if k in c['jy_slot'] else "0.0"
+            return bodies[ci][1 + c['n_jy'] + c['jp_slot'].index(k)] if k in c['jp_slot'] else "0.0"
         expr = of(last)
+        if all(of(ci) == expr for ci in range(last)):
+            return expr
         for ci in range(last - 1, -1, -1):
             expr = "SBM_SEL(is%d, %s, %s)" % (ci, of(ci), expr)
         return expr
 
     L.append("    f = %s;" % chain('f', 0))
-    for k in range(meta['max_jy']):
+    for k in range(n_slots['jy']):
         L.append("    jy[%d] = %s;" % (k, chain('jy', k)))
-    for k in range(meta['max_jp']):
+    for k in range(n_slots['jp']):
         L.append("    jp[%d] = %s;" % (k, chain('jp', k)))
+    return L
+
+
+def emit_rowlane_members(spec, d, meta, make_printer, hoist=True):
+    """Member functions of ``struct SbmModel`` for the row-lane kernel.  ``hoist=False``: every class body in full
+    (the reference form the shared one is checked against, tests/test_class_hoist.py)."""
+    n = spec.n_vars
+    classes = meta['classes']
+    L = ["  // ---- row-lane form (sbm_sens_rowlane_kernel) ----",
+         "  static constexpr int RL_NCLASS = %d;" % len(classes),
+         "  static constexpr int RL_MAXYS = %d, RL_MAXPS = %d, RL_MAXJY = %d, RL_MAXJP = %d;"
+         % (meta['max_ys'], meta['max_ps'], meta['max_jy'], meta['max_jp']),
+         "  static constexpr int RL_LARGEST_CLASS = %d;  // rows evaluated side by side" %
+         max(len(c['rows']) for c in classes),
+         "  // table accessors (the tables are namespace-scope __constant__ arrays above)",
+         "  __device__ __forceinline__ static int rl_class(int row) { return SBM_RL_CLASS[row]; }",
+         "  __device__ __forceinline__ static int rl_ys(int slot, int row) { return SBM_RL_YS[slot * NV + row]; }",
+         "  __device__ __forceinline__ static int rl_ps(int slot, int row) { return SBM_RL_PS[slot * NV + row]; }",
+         "  __device__ __forceinline__ static int rl_jyout(int slot, int row) { return SBM_RL_JYOUT[slot * NV + row]; }",
+         "  __device__ __forceinline__ static int rl_apos(int slot, int row) { return SBM_RL_APOS[slot * NV + row]; }",
+         "  __device__ __forceinline__ static int rl_jpcol(int slot, int row) { return SBM_RL_JPCOL[slot * NV + row]; }",
+         "  __device__ __forceinline__ static int rl_jycol(int slot, int row) { return SBM_RL_JYCOL[slot * NV + row]; }",
+         "  // one class body per distinct kinetic form; lane = row, operands per lane",
+         "  __device__ __forceinline__ static void class_dispatch(int cls, double t, const double (&ys)[RL_MAXYS],",
+         "                                                        const double (&ps)[RL_MAXPS], double& f,",
+         "                                                        double (&jy)[RL_MAXJY], double (&jp)[RL_MAXJP]) {",
+         "    (void)t; (void)ys; (void)ps;"]
+    L += _dispatch_body(classes, dict(ys=meta['max_ys'], ps=meta['max_ps'], jy=meta['max_jy'], jp=meta['max_jp']),
+                        make_printer, hoist=hoist, share_products=meta.get('share_products', False))
     # which (row lane, slot) holds J_y non-zero e; entries that depend on parameters only are
     # STATIC: the same for every stage of every step, broadcast once per kernel (rl_static)
     where = {}
@@ -381,7 +582,7 @@ def emit_rowlane_members(spec, d, meta, make_printer, hoist=True):
           "    (void)jy; (void)sj;"]
     for i in range(n):
         expr = "acol[%d]" % i
-        for e_idx, c in d.jy_rows[i]:
+        for e_idx, c in d.jy_base[i]:        # (summed in the order of the rows before alignment)
             if e_idx in static_idx:
                 expr = "fma(sj[%d], z[%d], %s)" % (static_idx[e_idx], c, expr)
             else:
@@ -397,8 +598,8 @@ def emit_rowlane_members(spec, d, meta, make_printer, hoist=True):
           "    (void)jyl;"]
     for i in range(n):
         expr = "acol[%d]" % i
-        for k, (e_idx, c) in enumerate(d.jy_rows[i]):
-            expr = "fma(jyl[%d], z[%d], %s)" % (i * meta['max_jy'] + k, c, expr)
+        for e_idx, c in d.jy_base[i]:
+            expr = "fma(jyl[%d], z[%d], %s)" % (i * meta['max_jy'] + where[e_idx][1], c, expr)
         L.append("    dz[%d] = %s;" % (i, expr))
     L += ["  }"]
     return L
