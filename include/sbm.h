@@ -439,6 +439,26 @@ int sbm_lm_trust_step_ex(sbm_ctx* ctx, const double* J_dev, const double* r_dev,
                          const double* theta_dev, double* trial_dev, double* delta_dev, double* pred_dev,
                          double* dxnorm_dev, double* gtx_dev, int32_t* status_dev);
 
+/* sbm_lm_trust_step_ex over the FREE parameters of every vector only (fits with held parameters, profile likelihoods:
+ * project/fitting.py `held=`, project/profiles.py).  An added export: SBM_ABI_VERSION is unchanged.
+ *   held [V][q]    nullable  != 0: parameter c of vector v does not move.  Masks differ from vector to vector within one
+ *                            launch.  NULL: exactly sbm_lm_trust_step_ex (the same kernel).
+ * The system is compacted, not masked: the nf free columns of a vector are gathered when the tile of J is staged, and
+ * the normal equations, the scaling D, lmpar's search with its factorisations, the clip, pred, dxnorm and gtx are those
+ * of the nf x nf problem -- the arithmetic of sbm_lm_trust_step_ex on J with the held columns deleted, in the same
+ * order (a vector with 60 of 68 parameters held pays for 8 Cholesky columns).  On return, for a held column:
+ * delta = 0, trial = theta (a copy), dscale = 0 -- so that sbm_lm_update's ||D theta|| is that of the free parameters;
+ * sbm_lm_update and sbm_lm_accept take these vectors as they are.  A non-finite entry in a held column of J is not
+ * looked at.  A vector with no free parameter is left like a skipped one (delta = 0, trial = theta, status 2; its dscale
+ * is zeroed): the caller marks it done.  A skipped vector is not touched at all, its dscale included.  Dynamic LDS
+ * as for sbm_lm_trust_step_ex, except that the row tile is chosen for a limit 576 bytes lower: the kernel's static LDS
+ * (304 bytes as in the unheld kernel + 272 for the list of free columns), so that both fit at every q (q = 128: 16 rows). */
+int sbm_lm_trust_step_held(sbm_ctx* ctx, const double* J_dev, const double* r_dev, double* dscale_dev,
+                           const double* radius_dev, double* lambda_dev, int32_t V, int32_t M, int32_t q,
+                           const double* row_scale_dev, const int32_t* skip_dev, double max_step,
+                           const double* theta_dev, double* trial_dev, double* delta_dev, double* pred_dev,
+                           double* dxnorm_dev, double* gtx_dev, int32_t* status_dev, const int32_t* held_dev);
+
 /* lmder's bookkeeping between two steps (MINPACK lmder.f, the loop around lmpar: what scipy.optimize.leastsq -- the
  * reference's optimiser, tests/test_Project.py:202-213, 351-357 -- does after every function evaluation), for V starts
  * in one launch: actual and predicted relative reduction, their ratio, the radius / lambda update (ratio <= 1/4: shrink

@@ -1,4 +1,4 @@
-// sbm_lm.hpp -- kernels of the fitting loop (include/sbm.h: sbm_lm_step, sbm_lm_trust_step[_ex], sbm_lm_update,
+// sbm_lm.hpp -- kernels of the fitting loop (include/sbm.h: sbm_lm_step, sbm_lm_trust_step[_ex|_held], sbm_lm_update,
 // sbm_lm_accept).  The two step kernels share the builder of the normal equations (lm_normal_equations) and the
 // factorisation (lm_cholesky / lm_forward / lm_backward); the host wrappers with the argument checks are in sbm_core.hip.
 #ifndef SBM_LM_HPP
@@ -36,9 +36,12 @@ struct LmTriangle {
 
 // The normal equations of diag(row_scale) J (row_scale nullable) and r, accumulated from row tiles staged in LDS
 // (T: [TILE][ld], rt: [TILE]).  *s_bad, in LDS and zeroed by the caller, is set on a non-finite entry; ends on a barrier.
+// GATHER: the system is built from the q columns idx[0..q) (in LDS, written before the call) of a J with rows of qs entries
+// -- column c of the tile is column idx[c] of J, everything after the staging is the same code on the same numbers.
+template <bool GATHER = false>
 __device__ __forceinline__ void lm_normal_equations(LmTriangle& n, int& n_own, double& gacc, const double* Jv, const double* rv,
                                                     const double* row_scale, int M, int q, int TILE, double* T, double* rt,
-                                                    int* s_bad, int tid) {
+                                                    int* s_bad, int tid, int qs = 0, const short* idx = nullptr) {
   const int ld = q + 1, n_low = q * (q + 1) / 2;
   n_own = 0;
   for (int e = tid; e < n_low; e += 256) {
@@ -54,7 +57,7 @@ __device__ __forceinline__ void lm_normal_equations(LmTriangle& n, int& n_own, d
     __syncthreads();
     for (int e = tid; e < rows * q; e += 256) {
       const int rr = e / q, c = e - rr * q;
-      double val = Jv[(size_t)(m0 + rr) * q + c];
+      double val = GATHER ? Jv[(size_t)(m0 + rr) * qs + idx[c]] : Jv[(size_t)(m0 + rr) * q + c];
       if (row_scale) val *= row_scale[m0 + rr];
       T[rr * ld + c] = val;
       if (!(fabs(val) < 1.0e300)) *s_bad = 1;
@@ -225,9 +228,52 @@ struct LmTrustArgs {
   double* trial;             // [V][q]
 };
 
-__global__ void __launch_bounds__(256) k_lm_trust(LmTrustArgs a) {
+// HELD = false is sbm_lm_trust_step[_ex]: qf = q, column c is column c.  HELD = true (sbm_lm_trust_step_held): the free
+// columns of the vector, idx[0..q) in ascending order, are compacted -- J is gathered through idx when its tile is staged
+// and from there on the kernel IS the HELD = false kernel on the q x q problem (leading dimension q + 1, thread t < q owns
+// free column idx[t], the same sums in the same order: the same bits as sbm_lm_trust_step_ex on J with the held columns
+// deleted), until the step is scattered back through idx.  A held column has no D, no g, no x: dscale = 0, delta = 0,
+// trial = theta (a copy) are written for it before anything else, so every way out of the kernel leaves them.
+// k_lm_update and k_lm_accept need no change for this: k_lm_update reads dscale only in ||D theta|| (exact zeros from
+// the held columns: lmder's xnorm of the reduced problem) and everything else per start; k_lm_accept copies trial rows,
+// whose held entries are theta's.
+template <bool HELD>
+__device__ __forceinline__ void lm_trust_body(LmTrustArgs a, const int32_t* held) {
   extern __shared__ __attribute__((aligned(16))) double lm_smem[];
-  const int v = blockIdx.x, tid = threadIdx.x, q = a.q, M = a.M, TILE = a.tile;
+  const int v = blockIdx.x, tid = threadIdx.x, qf = a.q, M = a.M, TILE = a.tile;
+  auto leave_alone = [&]() {                 // a skipped vector, or one with no free column: no step, status 2
+    for (int c = tid; c < qf; c += 256) {
+      a.delta[(size_t)v * qf + c] = 0.0;
+      if (a.trial && a.theta) a.trial[(size_t)v * qf + c] = a.theta[(size_t)v * qf + c];
+    }
+    if (tid == 0) { a.pred[v] = 0.0; a.dxnorm[v] = 0.0; a.status[v] = 2; if (a.gtx) a.gtx[v] = 0.0; }
+  };
+  int q = qf;                                // columns of the system that is solved
+  [[maybe_unused]] const short* idx = nullptr;
+  if constexpr (HELD) {
+    if (a.skip && a.skip[v]) { leave_alone(); return; }
+    // the free columns in ascending order: a ballot per wave (qf <= 128: waves 0 and 1 have columns), the waves' counts in LDS
+    __shared__ short s_idx[LM_MAX_Q];
+    __shared__ int s_cnt[4];
+    const bool is_free = tid < qf && held[(size_t)v * qf + tid] == 0;
+    const unsigned long long m = __ballot(is_free);
+    const int lane = tid & 63, wave = tid >> 6;
+    if (lane == 0) s_cnt[wave] = __popcll(m);
+    __syncthreads();
+    int base = 0;
+    for (int w = 0; w < wave; ++w) base += s_cnt[w];
+    q = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    if (is_free) s_idx[base + __popcll(m & ((1ull << lane) - 1ull))] = (short)tid;
+    if (tid < qf && !is_free) a.dscale[(size_t)v * qf + tid] = 0.0;
+    if (q == 0) { leave_alone(); return; }   // (uniform)
+    if (tid < qf && !is_free) {
+      a.delta[(size_t)v * qf + tid] = 0.0;
+      if (a.trial && a.theta) a.trial[(size_t)v * qf + tid] = a.theta[(size_t)v * qf + tid];
+    }
+    __syncthreads();
+    idx = s_idx;
+  }
+  auto col = [&](int c) -> int { if constexpr (HELD) return idx[c]; else return c; };   // column of J / theta behind column c
   const int ld = q + 1;
   double* A = lm_smem;                       // [q][ld]  the damped matrix / its Cholesky factor
   double* D = A + (size_t)q * ld;            // [q]      scaling
@@ -239,29 +285,24 @@ __global__ void __launch_bounds__(256) k_lm_trust(LmTrustArgs a) {
   double* rt = T + (size_t)TILE * ld;        // [TILE]
   __shared__ int s_bad;
   __shared__ double s_red[4];
-  if (a.skip && a.skip[v]) {
-    for (int c = tid; c < q; c += 256) {
-      a.delta[(size_t)v * q + c] = 0.0;
-      if (a.trial && a.theta) a.trial[(size_t)v * q + c] = a.theta[(size_t)v * q + c];
-    }
-    if (tid == 0) { a.pred[v] = 0.0; a.dxnorm[v] = 0.0; a.status[v] = 2; if (a.gtx) a.gtx[v] = 0.0; }
-    return;
-  }
+  if constexpr (!HELD)
+    if (a.skip && a.skip[v]) { leave_alone(); return; }
   if (tid == 0) s_bad = 0;
   LmTriangle n;
   int n_own;
   double gacc;
-  lm_normal_equations(n, n_own, gacc, a.J + (size_t)v * M * q, a.r + (size_t)v * M, a.row_scale, M, q, TILE, T, rt, &s_bad, tid);
+  lm_normal_equations<HELD>(n, n_own, gacc, a.J + (size_t)v * M * qf, a.r + (size_t)v * M, a.row_scale, M, q, TILE, T, rt, &s_bad,
+                            tid, qf, idx);
   const double Delta = a.radius[v];
   double lam = a.lambda[v];
   // scaling: the largest column norm seen so far (MINPACK mode 1); a column J never touches gets 1
   for (int k = 0; k < n_own; ++k)
     if (n.oi[k] == n.oj[k]) {
       const double cn = sqrt(fmax(n.acc[k], 0.0));
-      double d = fmax(a.dscale[(size_t)v * q + n.oi[k]], cn);
+      double d = fmax(a.dscale[(size_t)v * qf + col(n.oi[k])], cn);
       if (!(d > 0.0)) d = 1.0;
       D[n.oi[k]] = d;
-      a.dscale[(size_t)v * q + n.oi[k]] = d;
+      a.dscale[(size_t)v * qf + col(n.oi[k])] = d;
     }
   if (tid < q) g[tid] = gacc;
   __syncthreads();
@@ -341,9 +382,9 @@ __global__ void __launch_bounds__(256) k_lm_trust(LmTrustArgs a) {
     }
   }
   if (bad || !have) {
-    for (int c = tid; c < q; c += 256) {
-      a.delta[(size_t)v * q + c] = 0.0;
-      if (a.trial && a.theta) a.trial[(size_t)v * q + c] = a.theta[(size_t)v * q + c];
+    for (int c = tid; c < qf; c += 256) {
+      a.delta[(size_t)v * qf + c] = 0.0;
+      if (a.trial && a.theta) a.trial[(size_t)v * qf + c] = a.theta[(size_t)v * qf + c];
     }
     if (tid == 0) { a.pred[v] = 0.0; a.dxnorm[v] = 0.0; a.status[v] = 1; if (a.gtx) a.gtx[v] = 0.0; }
     return;
@@ -371,11 +412,17 @@ __global__ void __launch_bounds__(256) k_lm_trust(LmTrustArgs a) {
     tot = -gtx - 0.5 * block_sum(xhx, s_red);
   }
   if (tid < q) {
-    a.delta[(size_t)v * q + tid] = x[tid];
-    if (a.trial && a.theta) a.trial[(size_t)v * q + tid] = a.theta[(size_t)v * q + tid] + x[tid];
+    a.delta[(size_t)v * qf + col(tid)] = x[tid];
+    if (a.trial && a.theta) a.trial[(size_t)v * qf + col(tid)] = a.theta[(size_t)v * qf + col(tid)] + x[tid];
   }
   if (tid == 0) { a.pred[v] = tot; a.dxnorm[v] = dxn; a.lambda[v] = lam; a.status[v] = 0; if (a.gtx) a.gtx[v] = gtx; }
 }
+
+__global__ void __launch_bounds__(256) k_lm_trust(LmTrustArgs a) { lm_trust_body<false>(a, nullptr); }
+// held [V][q]: != 0 = the column does not move.  Static LDS: k_lm_trust's 304 bytes + 256 of the index list + 16 of the
+// waves' counts = LM_HELD_STATIC_LDS, which the host wrapper takes off the limit it chooses the row tile for.
+constexpr int LM_HELD_STATIC_LDS = 576;
+__global__ void __launch_bounds__(256) k_lm_trust_held(LmTrustArgs a, const int32_t* held) { lm_trust_body<true>(a, held); }
 
 // ---------------------------------------------------------------------------------------------
 // sbm_lm_update / sbm_lm_accept: lmder's bookkeeping between two trust-region steps, for V starts in two launches

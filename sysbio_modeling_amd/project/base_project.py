@@ -904,9 +904,19 @@ class Project(object):
 
     def fit_batch(self, thetas0, **options):
         """Multi-start Levenberg-Marquardt from every row of ``thetas0`` at once (project/fitting.py);
-        the batched counterpart of ``leastsq(self.residuals, x0, Dfun=self.calc_project_jacobian)``."""
+        the batched counterpart of ``leastsq(self.residuals, x0, Dfun=self.calc_project_jacobian)``.
+        ``held=``: parameters that stay at their starting values -- a bool mask (q,) or (V, q), a list of indices, or a
+        list of ``(p_group, settings)`` pairs."""
         from .fitting import levenberg_marquardt_batch
         return levenberg_marquardt_batch(self, thetas0, **options)
+
+    def profile_likelihood_batch(self, theta_hat, params='all', offsets=np.linspace(0.1, 2.0, 20), continuation=True,
+                                 stop_delta_chi2=None, **fit_options):
+        """Profile likelihoods of ``params`` around the optimum ``theta_hat``: every profile point a fit with one
+        parameter held, all branches of a grid step in one ``fit_batch(held=...)`` call (project/profiles.py)."""
+        from .profiles import profile_likelihood_batch
+        return profile_likelihood_batch(self, theta_hat, params=params, offsets=offsets, continuation=continuation,
+                                        stop_delta_chi2=stop_delta_chi2, **fit_options)
 
     def nlopt_fcn(self, project_param_vector, grad):
         """nlopt-style objective: fills ``grad`` in place when it is non-empty (reference :829-852)."""

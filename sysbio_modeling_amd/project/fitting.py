@@ -59,9 +59,52 @@ def _trial_budget(project, th, integrator_overrides, n_steps_sum=None, status=No
     return budget
 
 
+def normalize_held(held, V, q, project=None):
+    """The ``held`` argument of ``fit_batch`` as a (V, q) bool array (True: the parameter stays where the start has it).
+    Accepted: a bool array (q,) -- the same parameters in every start -- or (V, q); a list of parameter indices; a list of
+    ``(p_group, settings)`` pairs, resolved with ``project.get_param_index``.  ValueError on any other shape, an index
+    outside [-q, q) or a name the project does not know."""
+    arr = held if isinstance(held, np.ndarray) else None
+    if arr is None and hasattr(held, 'detach'):
+        arr = held.detach().cpu().numpy()
+    if arr is None:
+        items = list(held)
+        if items and all(isinstance(it, (tuple, list)) and len(it) == 2 and isinstance(it[0], str) for it in items):
+            if project is None:
+                raise ValueError("held: (p_group, settings) pairs need the project that names them")
+            idx = []
+            for group, settings in items:
+                try:
+                    found = project.get_param_index(group, settings)
+                except (KeyError, TypeError):
+                    raise ValueError("held: the project has no parameter %r / %r" % (group, settings)) from None
+                idx += list(found.values()) if isinstance(found, dict) else [found]
+            arr = np.asarray(idx, dtype=np.int64)
+        else:
+            try:
+                arr = np.asarray(items)
+            except ValueError:
+                raise ValueError("held: a bool array (q,) or (V, q), a list of indices or of (p_group, settings) pairs") from None
+            if arr.size == 0:
+                arr = arr.astype(np.int64)
+    if arr.dtype == np.bool_:
+        if arr.shape == (q,):
+            return np.ascontiguousarray(np.broadcast_to(arr, (V, q)))
+        if arr.shape == (V, q):
+            return np.ascontiguousarray(arr)
+        raise ValueError("held: a bool mask has shape (q,) = (%d,) or (V, q) = (%d, %d), not %s" % (q, V, q, arr.shape))
+    if arr.ndim != 1 or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError("held: a bool array (q,) or (V, q), a list of indices or of (p_group, settings) pairs")
+    if arr.size and (arr.min() < -q or arr.max() >= q):
+        raise ValueError("held: parameter index out of range for %d parameters: %s" % (q, arr[(arr < -q) | (arr >= q)].tolist()))
+    mask = np.zeros((q,), dtype=bool)
+    mask[arr] = True
+    return np.ascontiguousarray(np.broadcast_to(mask, (V, q)))
+
+
 def levenberg_marquardt_batch(project, thetas0, max_iter=60, lambda0=1e-2, lambda_up=4.0, lambda_down=3.0,
                               ftol=1.49012e-8, xtol=1.49012e-8, max_step=2.0, trace=False, lazy_jacobian='auto',
-                              algorithm='trust_region', factor=100.0, **integrator_overrides):
+                              algorithm='trust_region', factor=100.0, held=None, **integrator_overrides):
     """Minimise 0.5 |r(theta)|^2 from every row of ``thetas0`` (V, q), independently.
 
     ``algorithm='trust_region'`` (default since round 2): MINPACK's lmder, batched (`_trust_region_batch` below) -- the
@@ -95,16 +138,34 @@ def levenberg_marquardt_batch(project, thetas0, max_iter=60, lambda0=1e-2, lambd
     reported converged (costs and parameters are as good).  Pass ``lazy_jacobian=True`` together with looser
     ``ftol`` / tighter ``rtol`` where the saved sensitivity integrations matter.
 
+    ``held``: parameters that stay where the start has them while the others are fitted -- a bool mask (q,) or (V, q)
+    (a different set per start: the branches of a profile likelihood, project/profiles.py), a list of parameter indices, or
+    a list of ``(p_group, settings)`` pairs as ``get_param_index`` takes them (`normalize_held`).  Every step is lmder's on
+    the problem without the held columns (``sbm_lm_trust_step_held`` compacts the system per start: holding 60 of 68
+    parameters costs an 8 x 8 factorisation); the returned ``theta[:, held]`` is ``thetas0[:, held]`` bit for bit, a start
+    with nothing free comes back as it came, converged.  Supported with ``algorithm='trust_region'`` and an integration
+    that is one device call; ``held=None`` is the loop as it was.
+
     With a handful of starts the chip is mostly empty: ``variant='small_batch'`` (an integrator override) lets the
     sensitivity kernel use its small-batch split while starts x experiments x chunks <= 2048.
 
     Returns a dict of numpy arrays: theta (V, q), cost (V,) = 0.5 |r|^2, n_iter (V,) iterations until
     convergence (max_iter if never), converged (V,) bool, n_evaluations (total trial points integrated),
-    n_jacobian_evaluations (those integrated with sensitivities); with
+    n_jacobian_evaluations (those integrated with sensitivities); with ``held``, 'held' (V, q) bool; with
     ``trace=True`` also 'history': per iteration the number of accepted steps, starts still running, median cost,
     damping, relative decrease and largest step component (costs a device synchronisation per iteration).
     """
     import torch
+    if held is not None:
+        from .. import _control
+        one_call = str(project._options(**integrator_overrides).get('method', 'dopri45')).lower() \
+            not in _control.IMPLICIT_CONTROLLED + _control.AUTO
+        if algorithm not in ('trust_region', 'lmder', 'minpack') or not one_call:
+            raise ValueError("fit_batch: held parameters are supported by algorithm='trust_region' with an integration method "
+                             "that is one device call (not method='auto' / the host-controlled implicit methods); got "
+                             "algorithm=%r, method=%r" % (algorithm, project._options(**integrator_overrides).get('method')))
+        return _trust_region_fused(project, thetas0, max_iter=max_iter, ftol=ftol, xtol=xtol, factor=factor, trace=trace,
+                                   lazy_jacobian=lazy_jacobian, max_step=max_step, held=held, **integrator_overrides)
     if algorithm in ('trust_region', 'lmder', 'minpack', 'trust_region_torch'):
         # the loop's bookkeeping in two device launches per iteration (sbm_lm_update / sbm_lm_accept) whenever the
         # integration is ONE device call; the control loops of _control.py (method='auto', 'implicit_romberg') and
@@ -393,13 +454,18 @@ def _trust_region_batch(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
 
 
 def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.49012e-8, factor=100.0, trace=False,
-                        lazy_jacobian='auto', max_step=2.0, **integrator_overrides):
+                        lazy_jacobian='auto', max_step=2.0, held=None, **integrator_overrides):
     """`_trust_region_batch` with the bookkeeping on the device: per iteration ONE ``sbm_lm_trust_step_ex`` (lmpar, the
     clipped step and the trial point), the integration of the trial points (``sbm_jacobian_batch`` /
     ``sbm_residuals_batch`` into preallocated buffers), ONE ``sbm_lm_update`` (lmder's ratio / radius / acceptance /
     convergence logic) and ONE ``sbm_lm_accept`` (the accepted points' theta, r, J, cost) -- about eight launches and one
     4-byte read-back where round 2's loop issued ~70 tensor selects (68 000 micro-launches in a 100-iteration fit,
-    profiles/r02/fit_kernel_stats.csv).  Same algorithm, same numbers up to the order of a few sums."""
+    profiles/r02/fit_kernel_stats.csv).  Same algorithm, same numbers up to the order of a few sums.
+
+    ``held`` (see `levenberg_marquardt_batch`): the step comes from ``sbm_lm_trust_step_held`` with the (V, q) mask, the
+    initial radius factor * ||D theta|| is that of the free parameters, and a start with nothing free is done before the
+    first step.  ``sbm_lm_update`` and ``sbm_lm_accept`` are called as ever: held columns have dscale = 0 and
+    trial = theta."""
     import ctypes
     import warnings
     import torch
@@ -414,6 +480,10 @@ def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
     th = th.clone()
     dev = th.device
     V, q = th.shape
+    held_dev = None
+    if held is not None:
+        held = normalize_held(held, V, q, project)
+        held_dev = torch.from_numpy(held).to(dev)
     proj = project._device()
     R, M = project._n_residuals, project.n_total_rows
     G = len(project._loss_function.groups) if hasattr(project._loss_function, 'groups') else 0
@@ -454,14 +524,18 @@ def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
     row_scale = None
     if project.reference_compat:
         row_scale = torch.from_numpy(1.0 / project.descriptor_arrays()['row_sigma']).to(dev).contiguous()
-    done = bad.to(i32)
+    done = bad.to(i32) if held_dev is None else (bad | held_dev.all(dim=1)).to(i32)
     dscale = torch.zeros((V, q), dtype=f64, device=dev)
     lam = torch.zeros((V,), dtype=f64, device=dev)
     # lmder: D from the first Jacobian, Delta = factor * ||D theta|| (factor itself where that is zero)
     Js = cur['J'] if row_scale is None else cur['J'] * row_scale[None, :, None]
     col = torch.sqrt((Js * Js).sum(dim=1))
     del Js
-    xn = (torch.where(col > 0, col, torch.ones_like(col)) * th).norm(dim=1)
+    d0 = torch.where(col > 0, col, torch.ones_like(col))
+    if held_dev is not None:
+        d0 = torch.where(held_dev, torch.zeros_like(d0), d0)
+    xn = (d0 * th).norm(dim=1)
+    del d0
     radius = torch.where(xn > 0, factor * xn, torch.full_like(xn, float(factor))).contiguous()
     delta = torch.empty((V, q), dtype=f64, device=dev)
     trial = torch.empty((V, q), dtype=f64, device=dev)
@@ -470,13 +544,21 @@ def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
     st = torch.empty((V,), dtype=i32, device=dev)
     accept = torch.zeros((V,), dtype=i32, device=dev)
     n_iter = torch.full((V,), int(max_iter), dtype=i32, device=dev)
+    if held_dev is not None:
+        n_iter[held_dev.all(dim=1) & ~bad] = 0
     counters = torch.zeros((2,), dtype=i32, device=dev)
     n_eval, n_jac = V, V
     history = []
+    held_i32 = held_dev.to(i32).contiguous() if held_dev is not None else None
     for it in range(max_iter):
-        _lib.check(lib.sbm_lm_trust_step_ex(ctx.handle, p(cur['J']), p(cur['r']), p(dscale), p(radius), p(lam), V, M, q,
-                                            p(row_scale), p(done), float(max_step), p(th), p(trial), p(delta), p(pred),
-                                            p(dxnorm), p(gtx), p(st)), 'sbm_lm_trust_step_ex')
+        if held_i32 is None:
+            _lib.check(lib.sbm_lm_trust_step_ex(ctx.handle, p(cur['J']), p(cur['r']), p(dscale), p(radius), p(lam), V, M, q,
+                                                p(row_scale), p(done), float(max_step), p(th), p(trial), p(delta), p(pred),
+                                                p(dxnorm), p(gtx), p(st)), 'sbm_lm_trust_step_ex')
+        else:
+            _lib.check(lib.sbm_lm_trust_step_held(ctx.handle, p(cur['J']), p(cur['r']), p(dscale), p(radius), p(lam), V, M, q,
+                                                  p(row_scale), p(done), float(max_step), p(th), p(trial), p(delta), p(pred),
+                                                  p(dxnorm), p(gtx), p(st), p(held_i32)), 'sbm_lm_trust_step_held')
         if trace:
             import time
             torch.cuda.synchronize(dev)
@@ -539,4 +621,5 @@ def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
     torch.cuda.synchronize(dev)
     return {'theta': th.cpu().numpy(), 'cost': cost.cpu().numpy(), 'n_iter': n_iter.cpu().numpy().astype(np.int64),
             'converged': ((done != 0) & torch.isfinite(cost)).cpu().numpy(), 'n_evaluations': n_eval,
-            'n_jacobian_evaluations': n_jac, **({'history': history} if trace else {})}
+            'n_jacobian_evaluations': n_jac, **({'held': held} if held is not None else {}),
+            **({'history': history} if trace else {})}
