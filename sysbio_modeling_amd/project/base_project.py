@@ -27,6 +27,7 @@ import numpy as np
 from . import utils
 from .. import _lib
 from .. import _control
+from ._evaluation import DeviceEvaluator, finite_cost, one_device_call
 from .loss_functions.squared_loss import SquareLossFunction
 
 
@@ -650,11 +651,11 @@ class Project(object):
         (stiff ones) -- the control loops of ``_control.py``; the result then also carries 'stiff' (V,)
         bool.  Every other method is one device call.
         """
-        o = self._options(**integrator_overrides)
-        method = str(o.get('method', 'dopri45')).lower()
-        if method not in _control.IMPLICIT_CONTROLLED + _control.AUTO:
+        if one_device_call(self, integrator_overrides):
             return self._evaluate_once(thetas, jacobian, want, **integrator_overrides)
         import torch
+        o = self._options(**integrator_overrides)
+        method = str(o.get('method', 'dopri45')).lower()
         th, as_torch = self._theta_dev(thetas)
         V = th.shape[0]
         compare = ['sims'] + (['jacobian'] if jacobian else [])
@@ -711,43 +712,13 @@ class Project(object):
     def _evaluate_once(self, thetas, jacobian=False, want=('residuals',), **integrator_overrides):
         """One device call: all vectors with one integrator setting."""
         import torch
-        proj = self._device()
-        lib = _lib.load_library()
+        ev = DeviceEvaluator(self)
         th, as_torch = self._theta_dev(thetas)
-        dev = th.device
-        V, q = th.shape
-        R = self._n_residuals
-        RT = self.n_total_rows
-        G = self._n_sf_groups()
-        f64, i32 = torch.float64, torch.int32
-        out = {'residuals': torch.empty((V, RT), dtype=f64, device=dev),
-               'sims': torch.empty((V, R), dtype=f64, device=dev),
-               'sf': torch.empty((V, G), dtype=f64, device=dev),
-               'norms': torch.empty((V,), dtype=f64, device=dev),
-               'status': torch.empty((V,), dtype=i32, device=dev),
-               'n_steps': torch.empty((V,), dtype=i32, device=dev)}
-        opts = self._opts(**integrator_overrides)
-        p = _lib.dev_ptr
-        if not jacobian:
-            _lib.check(lib.sbm_residuals_batch(proj, p(th), V, ctypes.byref(opts), p(out['sims']),
-                                               p(out['residuals']), p(out['sf']) if G else None, p(out['norms']),
-                                               p(out['status']), p(out['n_steps'])), 'sbm_residuals_batch')
-        else:
-            out['jacobian'] = torch.empty((V, RT, q), dtype=f64, device=dev)
-            if 'model_jacobian' in want:
-                out['model_jacobian'] = torch.empty((V, R, q), dtype=f64, device=dev)
-            if 'gradient' in want:
-                out['gradient'] = torch.empty((V, q), dtype=f64, device=dev)
-            if 'sf_gradient' in want and G:
-                out['sf_gradient'] = torch.empty((V, G, q), dtype=f64, device=dev)
-            _lib.check(lib.sbm_jacobian_batch(proj, p(th), V, ctypes.byref(opts), p(out['sims']),
-                                              p(out['residuals']), p(out['jacobian']),
-                                              p(out.get('model_jacobian')), p(out['sf']) if G else None,
-                                              p(out.get('sf_gradient')), p(out['norms']), p(out.get('gradient')),
-                                              p(out['status']), p(out['n_steps'])), 'sbm_jacobian_batch')
+        out = ev.buffers(th.shape[0], jacobian, **{k: jacobian and k in want for k in ('model_jacobian', 'gradient', 'sf_gradient')})
+        ev.run(th, self._opts(**integrator_overrides), out, jacobian)
         if as_torch:
             return out
-        torch.cuda.synchronize(dev)
+        torch.cuda.synchronize(th.device)
         return {k: v.cpu().numpy() for k, v in out.items()}
 
     def _remember(self, theta, res, with_jac):
@@ -889,11 +860,9 @@ class Project(object):
         ``scipy.integrate.quad`` per vector and group (``device=False``, the default), or on the device
         (``device=True``: ``scale_factors_entropy_batch``; +inf where that gives -inf)."""
         if device:
-            import torch
             th, as_torch = self._theta_dev(thetas)
             res = self.evaluate_batch(th, want=('sims', 'norms', 'status'), **integrator_overrides)
-            out = 0.5 * res['norms'] - self.scale_factors_entropy_batch(res['sims'], temperature)
-            out = torch.where(torch.isfinite(out) & (res['status'] == 0), out, torch.full_like(out, float('inf')))
+            out = finite_cost(res['norms'], res['status'], self.scale_factors_entropy_batch(res['sims'], temperature))
             return out if as_torch else out.cpu().numpy()
         res = self.evaluate_batch(thetas, **integrator_overrides)
         out = 0.5 * res['norms']

@@ -23,6 +23,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._evaluation import DeviceEvaluator, finite_cost, inverse_row_sigma, one_device_call
+
 
 def sampling_axes(hessian, cutoff=0.0, temperature=1.0, step_scale=1.0):
     """Principal axes V (q, q) and step lengths s (q,) of the candidate density: a move is V @ (s * z), z standard
@@ -49,11 +51,6 @@ def sampling_matrix(hessian, cutoff=0.0, temperature=1.0, step_scale=1.0):
     """Candidate-move matrix M = V diag(s) of ``sampling_axes``: a move is M @ z, Gaussian with covariance M M^T."""
     V, s = sampling_axes(hessian, cutoff, temperature, step_scale)
     return V * s[..., None, :]
-
-
-def _inv_sigma(project):
-    """1 / sigma per measurement row where the project's Jacobian comes undivided by it, else None"""
-    return 1.0 / project.descriptor_arrays()['row_sigma'] if project.reference_compat else None
 
 
 def _gauss_newton_hessians(project, th, inv_sigma, overrides):
@@ -135,7 +132,7 @@ def ensemble_log_params_batch(project, params, hess=None, steps=1000, temperatur
                               integrator_overrides, recalc=recalc)
     if sampler == 'device':
         if hess is None:
-            hess = _gauss_newton_hessians(project, starts[:1], _inv_sigma(project), integrator_overrides)[0]
+            hess = _gauss_newton_hessians(project, starts[:1], inverse_row_sigma(project), integrator_overrides)[0]
         return _device_chains(project, starts, sampling_matrix(hess, sing_val_cutoff, temperature, step_scale), int(steps),
                               float(temperature), seeds, int(skip_elems), energy, draws, integrator_overrides)
     rng = np.random.default_rng(seeds)
@@ -146,7 +143,7 @@ def ensemble_log_params_batch(project, params, hess=None, steps=1000, temperatur
         out = 0.5 * project.evaluate_batch(th, **integrator_overrides)['norms']
         return np.where(np.isfinite(out), out, np.inf)
 
-    inv_sigma = _inv_sigma(project)
+    inv_sigma = inverse_row_sigma(project)
 
     def hessians(th):
         return _gauss_newton_hessians(project, th, inv_sigma, integrator_overrides)
@@ -200,44 +197,35 @@ def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems,
     chain keeps the axes (V, s, samp = V diag(s)) of its current point; per step five enqueues -- the evaluation is
     ``sbm_jacobian_batch``, ``sbm_sampling_axes`` turns the trial points' Jacobians into their axes, and
     ``sbm_mh_accept_hastings`` decides with the candidate density at both ends and moves the axes with the point."""
-    import ctypes
     import torch
-    from .. import _control, _lib
-    lib = _lib.load_library()
+    from .. import _lib
+    ev = DeviceEvaluator(project)
+    lib, proj, dev = ev.lib, ev.proj, ev.dev
     ctx = project._model.device_model.ctx
-    dev = torch.device('cuda', ctx.device)
-    proj = project._device()
     p = _lib.dev_ptr
     f64, i32 = torch.float64, torch.int32
     C, q = starts.shape
     free = energy == 'free_energy'
     if free:
         project._require_scale_factor_priors()
-    o = project._options(**overrides)
-    host_loop = str(o.get('method', 'dopri45')).lower() in _control.IMPLICIT_CONTROLLED + _control.AUTO
-    R, RT = project.n_project_residuals, project.n_total_rows
-    G = project._n_sf_groups()
+    host_loop = not one_device_call(project, overrides)
+    R, RT = ev.R, ev.RT
     curr = torch.from_numpy(np.ascontiguousarray(starts)).to(dev)
     trial = torch.empty_like(curr)
     if recalc is None:
         samp_d = torch.from_numpy(np.ascontiguousarray(samp, dtype=np.float64)).to(dev)
     else:
-        jac = torch.empty((C, RT, q), dtype=f64, device=dev)
         # axes of the current points and of the trial points: V, s, samp
         ax_c = [torch.empty(sh, dtype=f64, device=dev) for sh in ((C, q, q), (C, q), (C, q, q))]
         ax_t = [torch.empty(sh, dtype=f64, device=dev) for sh in ((C, q, q), (C, q), (C, q, q))]
         ax_status = torch.empty((C,), dtype=i32, device=dev)
         row_scale = None
-        inv_sigma = _inv_sigma(project)
+        inv_sigma = inverse_row_sigma(project)
         if inv_sigma is not None:       # the measurement rows of a reference_compat Jacobian come undivided by sigma
             row_scale = torch.ones((RT,), dtype=f64, device=dev)
             row_scale[:R] = torch.from_numpy(np.ascontiguousarray(inv_sigma, dtype=np.float64)).to(dev)
-    sims = torch.empty((C, R), dtype=f64, device=dev)
-    resid = torch.empty((C, RT), dtype=f64, device=dev)
-    sf = torch.empty((C, G), dtype=f64, device=dev) if G else None
-    norms = torch.empty((C,), dtype=f64, device=dev)
-    status = torch.empty((C,), dtype=i32, device=dev)
-    n_steps = torch.empty((C,), dtype=i32, device=dev)
+    buf = ev.buffers(C, jacobian=recalc is not None)
+    jac = buf.get('jacobian')
     entropy = torch.empty((C,), dtype=f64, device=dev) if free else None
     n_acc = torch.zeros((C,), dtype=i32, device=dev)
     opts = None if host_loop else project._opts(**overrides)
@@ -251,14 +239,9 @@ def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems,
             else:
                 res = project.evaluate_batch(th, want=('sims', 'norms', 'status'), **overrides)
             nr, st, sm = res['norms'].contiguous(), res['status'].to(i32).contiguous(), res['sims'].contiguous()
-        elif recalc is not None:
-            _lib.check(lib.sbm_jacobian_batch(proj, p(th), C, ctypes.byref(opts), p(sims), p(resid), p(jac), None, p(sf), None,
-                                              p(norms), None, p(status), p(n_steps)), 'sbm_jacobian_batch')
-            nr, st, sm = norms, status, sims
         else:
-            _lib.check(lib.sbm_residuals_batch(proj, p(th), C, ctypes.byref(opts), p(sims), p(resid), p(sf), p(norms),
-                                               p(status), p(n_steps)), 'sbm_residuals_batch')
-            nr, st, sm = norms, status, sims
+            ev.run(th, opts, buf, recalc is not None)
+            nr, st, sm = buf['norms'], buf['status'], buf['sims']
         if free:
             _lib.check(lib.sbm_project_sf_entropy(proj, p(sm), C, temperature, p(entropy), None), 'sbm_project_sf_entropy')
         return nr, st
@@ -273,8 +256,7 @@ def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems,
     nr, st = evaluate(curr)
     if recalc is not None:
         axes(ax_c, recalc['hess'])
-    F = 0.5 * nr - entropy if free else 0.5 * nr
-    F_curr = torch.where(torch.isfinite(F) & (st == 0), F, torch.full_like(F, float('inf'))).contiguous()
+    F_curr = finite_cost(nr, st, entropy).contiguous()
     every = skip_elems + 1
     n_kept = 1 + steps // every
     ens = torch.empty((n_kept, C, q), dtype=f64, device=dev)

@@ -14,6 +14,7 @@ from __future__ import annotations
 import numpy as np
 
 from .. import _lib
+from ._evaluation import DeviceEvaluator, finite_cost, inverse_row_sigma, one_device_call, usable
 
 
 def _trial_budget(project, th, integrator_overrides, n_steps_sum=None, status=None):
@@ -59,6 +60,22 @@ def _trial_budget(project, th, integrator_overrides, n_steps_sum=None, status=No
     return budget
 
 
+def is_param_pair(item):
+    """Whether ``item`` names parameters as ``(p_group, settings)``, the way ``Project.get_param_index`` takes them"""
+    return isinstance(item, (tuple, list)) and len(item) == 2 and isinstance(item[0], str)
+
+
+def param_pair_indices(project, pair, what):
+    """The parameter indices a ``(p_group, settings)`` pair names, as a list (every setting of the group with 'all').
+    ValueError, its message starting with ``what`` (the argument the pair came in), for a name the project does not know."""
+    group, settings = pair
+    try:
+        found = project.get_param_index(group, settings)
+    except (KeyError, TypeError):
+        raise ValueError("%s: the project has no parameter %r / %r" % (what, group, settings)) from None
+    return list(found.values()) if isinstance(found, dict) else [found]
+
+
 def normalize_held(held, V, q, project=None):
     """The ``held`` argument of ``fit_batch`` as a (V, q) bool array (True: the parameter stays where the start has it).
     Accepted: a bool array (q,) -- the same parameters in every start -- or (V, q); a list of parameter indices; a list of
@@ -69,17 +86,10 @@ def normalize_held(held, V, q, project=None):
         arr = held.detach().cpu().numpy()
     if arr is None:
         items = list(held)
-        if items and all(isinstance(it, (tuple, list)) and len(it) == 2 and isinstance(it[0], str) for it in items):
+        if items and all(is_param_pair(it) for it in items):
             if project is None:
                 raise ValueError("held: (p_group, settings) pairs need the project that names them")
-            idx = []
-            for group, settings in items:
-                try:
-                    found = project.get_param_index(group, settings)
-                except (KeyError, TypeError):
-                    raise ValueError("held: the project has no parameter %r / %r" % (group, settings)) from None
-                idx += list(found.values()) if isinstance(found, dict) else [found]
-            arr = np.asarray(idx, dtype=np.int64)
+            arr = np.asarray([i for it in items for i in param_pair_indices(project, it, 'held')], dtype=np.int64)
         else:
             try:
                 arr = np.asarray(items)
@@ -100,6 +110,114 @@ def normalize_held(held, V, q, project=None):
     mask = np.zeros((q,), dtype=bool)
     mask[arr] = True
     return np.ascontiguousarray(np.broadcast_to(mask, (V, q)))
+
+
+def _prepare(project, thetas0, lazy_jacobian):
+    """What the three loops below begin with: the refusal of prior rows under ``reference_compat``, ``lazy_jacobian`` resolved,
+    the library and the context (device, stream) the project's model lives on, and the starts staged on the device as a copy
+    the loop may write to.  Returns (th (V, q), V, q, device, lib, ctx, lazy_jacobian)."""
+    if project.reference_compat and project.n_total_rows != project.n_project_residuals:
+        raise ValueError("fit_batch needs reference_compat=False when priors are set: the reference leaves the "
+                         "prior rows of the Jacobian zero (SURVEY.md section 8a, quirk 4)")
+    if lazy_jacobian == 'auto':
+        lazy_jacobian = False        # (see levenberg_marquardt_batch: lazy is opt-in since round 3)
+    th, _ = project._theta_dev(np.asarray(thetas0, dtype=np.float64) if not hasattr(thetas0, 'device') else thetas0)
+    th = th.clone()
+    V, q = th.shape
+    return th, V, q, th.device, _lib.load_library(), project._model.device_model.ctx, lazy_jacobian
+
+
+def _inv_sigma_dev(project, dev):
+    """`inverse_row_sigma` on the device: reference_compat leaves J undivided by sigma (quirk 3) and the gradient needs
+    d r / d theta"""
+    import torch
+    inv_sigma = inverse_row_sigma(project)
+    return None if inv_sigma is None else torch.from_numpy(inv_sigma).to(dev)
+
+
+def _warn_unusable_starts(bad):
+    import warnings
+    warnings.warn("fit_batch: %d of %d starting points could not be integrated; they are returned as they came"
+                  % (int(bad.sum()), bad.numel()), stacklevel=2)
+
+
+def _evaluated_starts(project, th, overrides, warn):
+    """The start of the two tensor-select loops (the Marquardt loop, `_trust_region_batch`), which integrate through
+    ``evaluate_batch`` so that the host control loops of _control.py can serve them: ``evaluate(t)`` -> (r, J, cost) from one
+    state + sensitivity integration and ``cost_only(t)`` from a state-only one; the starts evaluated with the caller's / the
+    model's own step budget; then the budget of the trial points (`_trial_budget`, into ``overrides``, which both closures
+    read).  Returns (evaluate, cost_only, r, J, cost)."""
+    import torch
+    inv_sigma = _inv_sigma_dev(project, th.device)
+    last = {}
+
+    def evaluate(t):
+        out = project.evaluate_batch(t, jacobian=True, want=('jacobian',), **overrides)
+        last['n_steps'], last['status'] = out['n_steps'], out['status']
+        J = out['jacobian']
+        if inv_sigma is not None:
+            J = J * inv_sigma[None, :, None]
+        return out['residuals'], J, finite_cost(out['norms'], out['status'])
+
+    def cost_only(t):
+        out = project.evaluate_batch(t, **overrides)
+        return finite_cost(out['norms'], out['status'])
+
+    r, J, cost = evaluate(th)
+    if warn and not bool(torch.isfinite(cost).all()):
+        _warn_unusable_starts(~torch.isfinite(cost))
+    _trial_budget(project, th, overrides, n_steps_sum=last['n_steps'], status=last['status'])
+    return evaluate, cost_only, r, J, cost
+
+
+def _finite_stand_ins(J, r, cost):
+    """(J, r) with zeros where the current point is unusable (the steps of such starts are discarded), contiguous"""
+    import torch
+    fin = torch.isfinite(cost)
+    return (torch.where(fin[:, None, None], J, torch.zeros_like(J)).contiguous(),
+            torch.where(fin[:, None], r, torch.zeros_like(r)).contiguous())
+
+
+def _reintegrate_accepted(evaluate, keep, ok, trial, th, r, J, cost):
+    """``lazy_jacobian``: residuals and Jacobian of the accepted trial points ``ok``, from ONE integration each (so that
+    J^T r is consistent).  The state-only and the state + sensitivity integrations agree to the integrator's tolerance, not
+    to the bit: a point stays where it was unless ``keep(cost_a, cost_before)`` holds for its second cost.  Writes the
+    points kept into ``th``, ``r`` and ``J``; returns (the mask of the points kept, the new cost vector, the number of points
+    integrated)."""
+    import torch
+    sel = torch.nonzero(ok).flatten()
+    ok = torch.zeros_like(ok)
+    n = int(sel.numel())
+    if n:
+        r_a, J_a, cost_a = evaluate(trial[sel])
+        good = keep(cost_a, cost[sel])
+        sel, r_a, J_a, cost_a = sel[good], r_a[good], J_a[good], cost_a[good]
+        th[sel] = trial[sel]
+        r[sel] = r_a
+        J[sel] = J_a
+        cost = cost.clone()
+        cost[sel] = cost_a
+        ok[sel] = True
+    return ok, cost, n
+
+
+def _median_over(live):
+    """t -> the median of ``t`` over the starts ``live`` as a float (0.0 when there are none): the entries of ``trace``"""
+    some = bool(live.any())
+    return lambda t: float(t[live].median()) if some else 0.0
+
+
+def _result(th, cost, n_iter, done, n_eval, n_jac, history=None, held=None):
+    """The dict `levenberg_marquardt_batch` returns, from the loop's device tensors"""
+    import torch
+    out = {'theta': th.cpu().numpy(), 'cost': cost.cpu().numpy(), 'n_iter': n_iter.cpu().numpy().astype(np.int64),
+           'converged': (done.bool() & torch.isfinite(cost)).cpu().numpy(), 'n_evaluations': n_eval,
+           'n_jacobian_evaluations': n_jac}
+    if held is not None:
+        out['held'] = held
+    if history is not None:
+        out['history'] = history
+    return out
 
 
 def levenberg_marquardt_batch(project, thetas0, max_iter=60, lambda0=1e-2, lambda_up=4.0, lambda_down=3.0,
@@ -123,8 +241,8 @@ def levenberg_marquardt_batch(project, thetas0, max_iter=60, lambda0=1e-2, lambd
     Failed integrations (inf cost) count as rejections.  Two safeguards keep wild trial points from
     stalling the whole batch (one launch waits for its slowest trajectory): every component of a step is
     clipped to ``max_step`` log-units, and trial integrations get a step budget
-    (``max_steps``; default: five times what the starting points need, `_trial_budget`) -- a trial that exhausts it is
-    simply rejected.
+    (``max_steps``; default: three times -- six with DOP853 -- the attempts the slowest trajectory of the starting points
+    needs, at least 300, `_trial_budget`) -- a trial that exhausts it is simply rejected.
 
     ``lazy_jacobian``: a trial point is first integrated WITHOUT sensitivities (the state-only kernels: a
     tenth of the cost) to get its residuals; the state + sensitivity system is integrated only at the trial points that
@@ -155,62 +273,26 @@ def levenberg_marquardt_batch(project, thetas0, max_iter=60, lambda0=1e-2, lambd
     ``trace=True`` also 'history': per iteration the number of accepted steps, starts still running, median cost,
     damping, relative decrease and largest step component (costs a device synchronisation per iteration).
     """
-    import torch
-    if held is not None:
-        from .. import _control
-        one_call = str(project._options(**integrator_overrides).get('method', 'dopri45')).lower() \
-            not in _control.IMPLICIT_CONTROLLED + _control.AUTO
-        if algorithm not in ('trust_region', 'lmder', 'minpack') or not one_call:
-            raise ValueError("fit_batch: held parameters are supported by algorithm='trust_region' with an integration method "
-                             "that is one device call (not method='auto' / the host-controlled implicit methods); got "
-                             "algorithm=%r, method=%r" % (algorithm, project._options(**integrator_overrides).get('method')))
-        return _trust_region_fused(project, thetas0, max_iter=max_iter, ftol=ftol, xtol=xtol, factor=factor, trace=trace,
-                                   lazy_jacobian=lazy_jacobian, max_step=max_step, held=held, **integrator_overrides)
+    # the loop's bookkeeping in two device launches per iteration (sbm_lm_update / sbm_lm_accept) whenever the integration is
+    # ONE device call; the control loops of _control.py (method='auto', 'implicit_romberg') and algorithm='trust_region_torch'
+    # (round 2's spelling in tensor selects, kept as the cross-check) take the other
+    fused = algorithm in ('trust_region', 'lmder', 'minpack') and one_device_call(project, integrator_overrides)
+    if held is not None and not fused:
+        raise ValueError("fit_batch: held parameters are supported by algorithm='trust_region' with an integration method "
+                         "that is one device call (not method='auto' / the host-controlled implicit methods); got "
+                         "algorithm=%r, method=%r" % (algorithm, project._options(**integrator_overrides).get('method')))
     if algorithm in ('trust_region', 'lmder', 'minpack', 'trust_region_torch'):
-        # the loop's bookkeeping in two device launches per iteration (sbm_lm_update / sbm_lm_accept) whenever the
-        # integration is ONE device call; the control loops of _control.py (method='auto', 'implicit_romberg') and
-        # algorithm='trust_region_torch' (round 2's spelling in tensor selects, kept as the cross-check) take the other
-        from .. import _control
-        o = project._options(**integrator_overrides)
-        one_call = str(o.get('method', 'dopri45')).lower() not in _control.IMPLICIT_CONTROLLED + _control.AUTO
-        fn = _trust_region_fused if (one_call and algorithm != 'trust_region_torch') else _trust_region_batch
-        return fn(project, thetas0, max_iter=max_iter, ftol=ftol, xtol=xtol, factor=factor, trace=trace,
-                  lazy_jacobian=lazy_jacobian, max_step=max_step, **integrator_overrides)
+        fit = dict(max_iter=max_iter, ftol=ftol, xtol=xtol, factor=factor, trace=trace, lazy_jacobian=lazy_jacobian,
+                   max_step=max_step)
+        if fused:
+            return _trust_region_fused(project, thetas0, held=held, **fit, **integrator_overrides)
+        return _trust_region_batch(project, thetas0, **fit, **integrator_overrides)
     if algorithm != 'marquardt':
         raise ValueError("fit_batch: unknown algorithm %r ('marquardt', 'trust_region' or 'trust_region_torch')" % (algorithm,))
-    if lazy_jacobian == 'auto':
-        lazy_jacobian = False        # (see levenberg_marquardt_batch: lazy is opt-in since round 3)
-    if project.reference_compat and project.n_total_rows != project.n_project_residuals:
-        raise ValueError("fit_batch needs reference_compat=False when priors are set: the reference leaves the "
-                         "prior rows of the Jacobian zero (SURVEY.md section 8a, quirk 4)")
-    lib = _lib.load_library()
-    ctx = project._model.device_model.ctx      # the context (device, stream) the project's model lives on
-    th, _ = project._theta_dev(np.asarray(thetas0, dtype=np.float64) if not hasattr(thetas0, 'device') else thetas0)
-    th = th.clone()
-    dev = th.device
-    V, q = th.shape
+    import torch
+    th, V, q, dev, lib, ctx, lazy_jacobian = _prepare(project, thetas0, lazy_jacobian)
     f64, i32 = torch.float64, torch.int32
-    want = ('jacobian',)
-    # reference_compat leaves J undivided by sigma (quirk 3): divide here, the gradient needs d r / d theta
-    inv_sigma = None
-    if project.reference_compat:
-        a = project.descriptor_arrays()
-        inv_sigma = torch.from_numpy(1.0 / a['row_sigma']).to(dev)
-
-    last = {}
-
-    def evaluate(t):
-        out = project.evaluate_batch(t, jacobian=True, want=want, **integrator_overrides)
-        last['n_steps'], last['status'] = out['n_steps'], out['status']
-        J = out['jacobian']
-        if inv_sigma is not None:
-            J = J * inv_sigma[None, :, None]
-        cost = 0.5 * out['norms']
-        cost = torch.where(torch.isfinite(cost) & (out['status'] == 0), cost, torch.full_like(cost, float('inf')))
-        return out['residuals'], J, cost
-
-    r, J, cost = evaluate(th)            # the starting points: the caller's / the model's own step budget
-    _trial_budget(project, th, integrator_overrides, n_steps_sum=last['n_steps'], status=last['status'])
+    evaluate, cost_only, r, J, cost = _evaluated_starts(project, th, integrator_overrides, warn=False)
     M = r.shape[1]
     lam = torch.full((V,), float(lambda0), dtype=f64, device=dev)
     delta = torch.empty((V, q), dtype=f64, device=dev)
@@ -223,18 +305,14 @@ def levenberg_marquardt_batch(project, thetas0, max_iter=60, lambda0=1e-2, lambd
     history = []
     p = _lib.dev_ptr
     for it in range(max_iter):
-        # finite stand-ins where the current point is unusable (their steps are discarded below)
-        Jc = torch.where(torch.isfinite(cost)[:, None, None], J, torch.zeros_like(J)).contiguous()
-        rc = torch.where(torch.isfinite(cost)[:, None], r, torch.zeros_like(r)).contiguous()
+        Jc, rc = _finite_stand_ins(J, r, cost)
         _lib.check(lib.sbm_lm_step(ctx.handle, p(Jc), p(rc), p(lam), V, M, q, p(delta), p(pred), p(st)), 'sbm_lm_step')
         # per parameter, not by shrinking the whole step: a parameter the data barely constrain gets an
         # enormous (and harmless) Gauss-Newton step, which must not scale everybody else's down to nothing
         delta = delta.clamp(-max_step, max_step)
         trial = torch.where(done[:, None], th, th + delta)
         if lazy_jacobian:
-            out_t = project.evaluate_batch(trial, **integrator_overrides)
-            cost_t = 0.5 * out_t['norms']
-            cost_t = torch.where(torch.isfinite(cost_t) & (out_t['status'] == 0), cost_t, torch.full_like(cost_t, float('inf')))
+            cost_t = cost_only(trial)
         else:
             r_t, J_t, cost_t = evaluate(trial)
         n_eval += V
@@ -247,24 +325,9 @@ def levenberg_marquardt_batch(project, thetas0, max_iter=60, lambda0=1e-2, lambd
         small_x = (st == 0) & ~done & free & (delta.abs() <= xtol * (th.abs() + xtol)).all(dim=1)
         cost_prev = cost
         if lazy_jacobian:
-            # residuals and Jacobian of the accepted points, from ONE integration each (so that J^T r is consistent)
-            sel = torch.nonzero(ok).flatten()
-            if sel.numel():
-                r_a, J_a, cost_a = evaluate(trial[sel])
-                n_jac += int(sel.numel())
-                # (the state-only and the state + sensitivity integrations agree to the integrator's tolerance, not to
-                # the bit: a point whose second integration fails or no longer improves stays where it was)
-                good = torch.isfinite(cost_a) & (cost_a < cost[sel])
-                sel, r_a, J_a, cost_a = sel[good], r_a[good], J_a[good], cost_a[good]
-                th[sel] = trial[sel]
-                r[sel] = r_a
-                J[sel] = J_a
-                cost = cost.clone()
-                cost[sel] = cost_a
-                ok = torch.zeros_like(ok)
-                ok[sel] = True
-            else:
-                ok = torch.zeros_like(ok)
+            # (a point whose second integration fails or no longer improves stays where it was)
+            ok, cost, n = _reintegrate_accepted(evaluate, lambda c_a, c: torch.isfinite(c_a) & (c_a < c), ok, trial, th, r, J, cost)
+            n_jac += n
         else:
             th = torch.where(ok[:, None], trial, th)
             r = torch.where(ok[:, None], r_t, r)
@@ -275,18 +338,16 @@ def levenberg_marquardt_batch(project, thetas0, max_iter=60, lambda0=1e-2, lambd
         newly = (small_f | small_x) & ~done
         if trace:
             live = ~done
+            md = _median_over(live)
             history.append(dict(iteration=it, accepted=int((ok & live).sum()), live=int(live.sum()),
-                                cost_median=float(cost.median()), lambda_median=float(lam[live].median()) if bool(live.any()) else 0.0,
-                                rel_decrease_median=float(((cost_prev - cost) / cost_prev)[live].median()) if bool(live.any()) else 0.0,
-                                step_max_median=float(delta.abs().max(dim=1).values[live].median()) if bool(live.any()) else 0.0))
+                                cost_median=float(cost.median()), lambda_median=md(lam),
+                                rel_decrease_median=md((cost_prev - cost) / cost_prev),
+                                step_max_median=md(delta.abs().max(dim=1).values)))
         n_iter = torch.where(newly, torch.full_like(n_iter, it + 1), n_iter)
         done = done | newly
         if bool(done.all()):
             break
-    return {'theta': th.cpu().numpy(), 'cost': cost.cpu().numpy(), 'n_iter': n_iter.cpu().numpy(),
-            'converged': (done & torch.isfinite(cost)).cpu().numpy(), 'n_evaluations': n_eval,
-            'n_jacobian_evaluations': n_jac,
-            **({'history': history} if trace else {})}
+    return _result(th, cost, n_iter, done, n_eval, n_jac, history if trace else None)
 
 
 def _trust_region_batch(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.49012e-8, factor=100.0, trace=False,
@@ -305,45 +366,9 @@ def _trust_region_batch(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
     that cannot be integrated counts as an increase of the cost.  ``max_step`` only keeps exp(theta) finite.
     """
     import torch
-    if project.reference_compat and project.n_total_rows != project.n_project_residuals:
-        raise ValueError("fit_batch needs reference_compat=False when priors are set: the reference leaves the "
-                         "prior rows of the Jacobian zero (SURVEY.md section 8a, quirk 4)")
-    if lazy_jacobian == 'auto':
-        lazy_jacobian = False        # (see levenberg_marquardt_batch: lazy is opt-in since round 3)
-    lib = _lib.load_library()
-    ctx = project._model.device_model.ctx
-    th, _ = project._theta_dev(np.asarray(thetas0, dtype=np.float64) if not hasattr(thetas0, 'device') else thetas0)
-    th = th.clone()
-    dev = th.device
-    V, q = th.shape
+    th, V, q, dev, lib, ctx, lazy_jacobian = _prepare(project, thetas0, lazy_jacobian)
     f64, i32 = torch.float64, torch.int32
-    inv_sigma = None
-    if project.reference_compat:
-        inv_sigma = torch.from_numpy(1.0 / project.descriptor_arrays()['row_sigma']).to(dev)
-
-    last = {}
-
-    def evaluate(t):
-        out = project.evaluate_batch(t, jacobian=True, want=('jacobian',), **integrator_overrides)
-        last['n_steps'], last['status'] = out['n_steps'], out['status']
-        J = out['jacobian']
-        if inv_sigma is not None:
-            J = J * inv_sigma[None, :, None]
-        c = 0.5 * out['norms']
-        c = torch.where(torch.isfinite(c) & (out['status'] == 0), c, torch.full_like(c, float('inf')))
-        return out['residuals'], J, c
-
-    def cost_only(t):
-        out = project.evaluate_batch(t, **integrator_overrides)
-        c = 0.5 * out['norms']
-        return torch.where(torch.isfinite(c) & (out['status'] == 0), c, torch.full_like(c, float('inf')))
-
-    r, J, cost = evaluate(th)            # the starting points: the caller's / the model's own step budget
-    if not bool(torch.isfinite(cost).all()):
-        import warnings
-        warnings.warn("fit_batch: %d of %d starting points could not be integrated; they are returned as they came"
-                      % (int((~torch.isfinite(cost)).sum()), V))
-    _trial_budget(project, th, integrator_overrides, n_steps_sum=last['n_steps'], status=last['status'])
+    evaluate, cost_only, r, J, cost = _evaluated_starts(project, th, integrator_overrides, warn=True)
     M = r.shape[1]
     done = ~torch.isfinite(cost)
     dscale = torch.zeros((V, q), dtype=f64, device=dev)
@@ -359,8 +384,7 @@ def _trust_region_batch(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
     p = _lib.dev_ptr
     first = True
     for it in range(max_iter):
-        Jc = torch.where(torch.isfinite(cost)[:, None, None], J, torch.zeros_like(J)).contiguous()
-        rc = torch.where(torch.isfinite(cost)[:, None], r, torch.zeros_like(r)).contiguous()
+        Jc, rc = _finite_stand_ins(J, r, cost)
         if first:
             # lmder: D from the first Jacobian, Delta = factor * ||D theta|| (factor itself where that is zero)
             col = torch.sqrt((Jc * Jc).sum(dim=1))
@@ -414,19 +438,8 @@ def _trust_region_batch(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
         cost_prev = cost
         th_before = th.clone() if lazy_jacobian else th
         if lazy_jacobian:
-            sel = torch.nonzero(ok).flatten()
-            ok = torch.zeros_like(ok)
-            if sel.numel():
-                r_a, J_a, cost_a = evaluate(trial[sel])
-                n_jac += int(sel.numel())
-                good = torch.isfinite(cost_a)
-                sel, r_a, J_a, cost_a = sel[good], r_a[good], J_a[good], cost_a[good]
-                th[sel] = trial[sel]
-                r[sel] = r_a
-                J[sel] = J_a
-                cost = cost.clone()
-                cost[sel] = cost_a
-                ok[sel] = True
+            ok, cost, n = _reintegrate_accepted(evaluate, lambda c_a, c: torch.isfinite(c_a), ok, trial, th, r, J, cost)
+            n_jac += n
         else:
             th = torch.where(ok[:, None], trial, th)
             r = torch.where(ok[:, None], r_t, r)
@@ -440,7 +453,7 @@ def _trust_region_batch(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
         newly = (conv_f | conv_x) & ~done
         if trace:
             live = ~done
-            md = lambda t: float(t[live].median()) if bool(live.any()) else 0.0
+            md = _median_over(live)
             history.append(dict(iteration=it, accepted=int((ok & live).sum()), live=int(live.sum()), cost_median=float(cost.median()),
                                 lambda_median=md(lam), radius_median=md(radius), ratio_median=md(ratio),
                                 rel_decrease_median=md((cost_prev - cost) / cost_prev)))
@@ -448,9 +461,7 @@ def _trust_region_batch(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
         done = done | newly
         if bool(done.all()):
             break
-    return {'theta': th.cpu().numpy(), 'cost': cost.cpu().numpy(), 'n_iter': n_iter.cpu().numpy(),
-            'converged': (done & torch.isfinite(cost)).cpu().numpy(), 'n_evaluations': n_eval,
-            'n_jacobian_evaluations': n_jac, **({'history': history} if trace else {})}
+    return _result(th, cost, n_iter, done, n_eval, n_jac, history if trace else None)
 
 
 def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.49012e-8, factor=100.0, trace=False,
@@ -466,69 +477,33 @@ def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
     initial radius factor * ||D theta|| is that of the free parameters, and a start with nothing free is done before the
     first step.  ``sbm_lm_update`` and ``sbm_lm_accept`` are called as ever: held columns have dscale = 0 and
     trial = theta."""
-    import ctypes
-    import warnings
     import torch
-    if project.reference_compat and project.n_total_rows != project.n_project_residuals:
-        raise ValueError("fit_batch needs reference_compat=False when priors are set: the reference leaves the "
-                         "prior rows of the Jacobian zero (SURVEY.md section 8a, quirk 4)")
-    if lazy_jacobian == 'auto':
-        lazy_jacobian = False        # (see levenberg_marquardt_batch: lazy is opt-in since round 3)
-    lib = _lib.load_library()
-    ctx = project._model.device_model.ctx
-    th, _ = project._theta_dev(np.asarray(thetas0, dtype=np.float64) if not hasattr(thetas0, 'device') else thetas0)
-    th = th.clone()
-    dev = th.device
-    V, q = th.shape
+    th, V, q, dev, lib, ctx, lazy_jacobian = _prepare(project, thetas0, lazy_jacobian)
     held_dev = None
     if held is not None:
         held = normalize_held(held, V, q, project)
         held_dev = torch.from_numpy(held).to(dev)
-    proj = project._device()
-    R, M = project._n_residuals, project.n_total_rows
-    G = len(project._loss_function.groups) if hasattr(project._loss_function, 'groups') else 0
+    ev = DeviceEvaluator(project)
+    M = ev.RT
     f64, i32 = torch.float64, torch.int32
     p = _lib.dev_ptr
-
-    def buffers(n, with_J=True):
-        b = dict(sims=torch.empty((n, R), dtype=f64, device=dev), r=torch.empty((n, M), dtype=f64, device=dev),
-                 sf=torch.empty((n, max(G, 1)), dtype=f64, device=dev), norms=torch.empty((n,), dtype=f64, device=dev),
-                 status=torch.empty((n,), dtype=i32, device=dev), nsteps=torch.empty((n,), dtype=i32, device=dev))
-        if with_J:
-            b['J'] = torch.empty((n, M, q), dtype=f64, device=dev)
-        return b
-
-    def integrate(theta_t, opts, b, jac):
-        n = theta_t.shape[0]
-        if jac:
-            _lib.check(lib.sbm_jacobian_batch(proj, p(theta_t), n, ctypes.byref(opts), p(b['sims']), p(b['r']), p(b['J']), None,
-                                              p(b['sf']) if G else None, None, p(b['norms']), None, p(b['status']),
-                                              p(b['nsteps'])), 'sbm_jacobian_batch')
-        else:
-            _lib.check(lib.sbm_residuals_batch(proj, p(theta_t), n, ctypes.byref(opts), p(b['sims']), p(b['r']),
-                                               p(b['sf']) if G else None, p(b['norms']), p(b['status']), p(b['nsteps'])),
-                       'sbm_residuals_batch')
-
-    cur, tr = buffers(V), buffers(V)
-    integrate(th, project._opts(**integrator_overrides), cur, True)      # the starts: the caller's / the model's own budget
-    cost = torch.where(torch.isfinite(cur['norms']) & (cur['status'] == 0), 0.5 * cur['norms'],
-                       torch.full_like(cur['norms'], float('inf')))
+    cur, tr = ev.buffers(V, jacobian=True), ev.buffers(V, jacobian=True)
+    ev.run(th, project._opts(**integrator_overrides), cur, True)      # the starts: the caller's / the model's own budget
+    cost = finite_cost(cur['norms'], cur['status'])
     bad = ~torch.isfinite(cost)
+    cur_J, cur_r = cur['jacobian'], cur['residuals']
     if bool(bad.any()):
-        warnings.warn("fit_batch: %d of %d starting points could not be integrated; they are returned as they came"
-                      % (int(bad.sum()), V))
-        cur['J'][bad] = 0.0
-        cur['r'][bad] = 0.0
-    _trial_budget(project, th, integrator_overrides, n_steps_sum=cur['nsteps'], status=cur['status'])
+        _warn_unusable_starts(bad)
+        cur_J[bad] = 0.0
+        cur_r[bad] = 0.0
+    _trial_budget(project, th, integrator_overrides, n_steps_sum=cur['n_steps'], status=cur['status'])
     opts_t = project._opts(**integrator_overrides)
-    row_scale = None
-    if project.reference_compat:
-        row_scale = torch.from_numpy(1.0 / project.descriptor_arrays()['row_sigma']).to(dev).contiguous()
+    row_scale = _inv_sigma_dev(project, dev)
     done = bad.to(i32) if held_dev is None else (bad | held_dev.all(dim=1)).to(i32)
     dscale = torch.zeros((V, q), dtype=f64, device=dev)
     lam = torch.zeros((V,), dtype=f64, device=dev)
     # lmder: D from the first Jacobian, Delta = factor * ||D theta|| (factor itself where that is zero)
-    Js = cur['J'] if row_scale is None else cur['J'] * row_scale[None, :, None]
+    Js = cur_J if row_scale is None else cur_J * row_scale[None, :, None]
     col = torch.sqrt((Js * Js).sum(dim=1))
     del Js
     d0 = torch.where(col > 0, col, torch.ones_like(col))
@@ -552,25 +527,25 @@ def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
     held_i32 = held_dev.to(i32).contiguous() if held_dev is not None else None
     for it in range(max_iter):
         if held_i32 is None:
-            _lib.check(lib.sbm_lm_trust_step_ex(ctx.handle, p(cur['J']), p(cur['r']), p(dscale), p(radius), p(lam), V, M, q,
+            _lib.check(lib.sbm_lm_trust_step_ex(ctx.handle, p(cur_J), p(cur_r), p(dscale), p(radius), p(lam), V, M, q,
                                                 p(row_scale), p(done), float(max_step), p(th), p(trial), p(delta), p(pred),
                                                 p(dxnorm), p(gtx), p(st)), 'sbm_lm_trust_step_ex')
         else:
-            _lib.check(lib.sbm_lm_trust_step_held(ctx.handle, p(cur['J']), p(cur['r']), p(dscale), p(radius), p(lam), V, M, q,
+            _lib.check(lib.sbm_lm_trust_step_held(ctx.handle, p(cur_J), p(cur_r), p(dscale), p(radius), p(lam), V, M, q,
                                                   p(row_scale), p(done), float(max_step), p(th), p(trial), p(delta), p(pred),
                                                   p(dxnorm), p(gtx), p(st), p(held_i32)), 'sbm_lm_trust_step_held')
         if trace:
             import time
             torch.cuda.synchronize(dev)
             t_launch = time.perf_counter()
-        integrate(trial, opts_t, tr, not lazy_jacobian)
+        ev.run(trial, opts_t, tr, not lazy_jacobian)
         n_eval += V
         if trace:
             # what the trial launch cost and why: it lasts as long as its slowest trajectory (scripts/dev_fit_trace.py)
             torch.cuda.synchronize(dev)
             t_launch = time.perf_counter() - t_launch
             per = torch.empty((V, max(1, len(project._experiments))), dtype=i32, device=dev)
-            _lib.check(lib.sbm_project_trajectory_steps(proj, V, p(per)), 'sbm_project_trajectory_steps')
+            _lib.check(lib.sbm_project_trajectory_steps(ev.proj, V, p(per)), 'sbm_project_trajectory_steps')
             launch = dict(ms=1e3 * t_launch, steps_max=int(per.max()), steps_mean=float(per.double().mean()),
                           steps_p99=float(per.double().flatten().quantile(0.99)), failed=int((tr['status'] != 0).sum()),
                           done=int((done != 0).sum()))
@@ -583,10 +558,10 @@ def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
             # MINPACK's economy: the state + sensitivity system only at the trial points that were accepted
             sel = torch.nonzero(accept).flatten()
             if sel.numel():
-                sub = buffers(int(sel.numel()))
-                integrate(trial[sel].contiguous(), opts_t, sub, True)
+                sub = ev.buffers(int(sel.numel()), jacobian=True)
+                ev.run(trial[sel].contiguous(), opts_t, sub, True)
                 n_jac += int(sel.numel())
-                good = torch.isfinite(sub['norms']) & (sub['status'] == 0)
+                good = usable(sub['norms'], sub['status'])
                 vetoed = sel[~good]
                 accept[vetoed] = 0
                 # sbm_lm_update ran BEFORE this re-integration: a start whose accepted step is vetoed here (the sensitivity
@@ -596,30 +571,22 @@ def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
                 if veto_live:
                     done[vetoed] = 0
                     n_iter[vetoed] = int(max_iter)
-                tr['r'][sel] = sub['r']
+                tr['residuals'][sel] = sub['residuals']
                 tr['norms'][sel] = sub['norms']
-                if 'J' not in tr:
-                    tr['J'] = torch.empty((V, M, q), dtype=f64, device=dev)
-                tr['J'][sel] = sub['J']
-            elif 'J' not in tr:
-                tr['J'] = torch.empty((V, M, q), dtype=f64, device=dev)
+                tr['jacobian'][sel] = sub['jacobian']
         else:
             n_jac += V
-        _lib.check(lib.sbm_lm_accept(ctx.handle, p(accept), V, M, q, p(trial), p(tr['r']), p(tr['J']), p(tr['norms']), p(th),
-                                     p(cur['r']), p(cur['J']), p(cost)), 'sbm_lm_accept')
+        _lib.check(lib.sbm_lm_accept(ctx.handle, p(accept), V, M, q, p(trial), p(tr['residuals']), p(tr['jacobian']), p(tr['norms']),
+                                     p(th), p(cur_r), p(cur_J), p(cost)), 'sbm_lm_accept')
         live, n_acc = (int(x) for x in counters.cpu())          # (the one read-back of the iteration)
         if lazy_jacobian and veto_live:
             live, n_acc = int((done == 0).sum()), n_acc - veto_live
         if trace:
-            running = done == 0
-            md = lambda t: float(t[running].median()) if bool(running.any()) else 0.0     # noqa: E731
+            md = _median_over(done == 0)
             history.append(dict(iteration=it, accepted=n_acc, live=live, launch=launch, cost_median=float(cost.median()),
                                 lambda_median=md(lam), radius_median=md(radius), ratio_median=md(ratio),
                                 rel_decrease_median=md((cost_prev - cost) / cost_prev)))
         if live == 0:
             break
     torch.cuda.synchronize(dev)
-    return {'theta': th.cpu().numpy(), 'cost': cost.cpu().numpy(), 'n_iter': n_iter.cpu().numpy().astype(np.int64),
-            'converged': ((done != 0) & torch.isfinite(cost)).cpu().numpy(), 'n_evaluations': n_eval,
-            'n_jacobian_evaluations': n_jac, **({'held': held} if held is not None else {}),
-            **({'history': history} if trace else {})}
+    return _result(th, cost, n_iter, done, n_eval, n_jac, history if trace else None, held)

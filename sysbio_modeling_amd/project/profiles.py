@@ -13,6 +13,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from .fitting import is_param_pair, param_pair_indices
+
 # what fit_batch itself consumes; everything else in **fit_options is an integrator override (method, rtol, ...)
 _FIT_KEYS = ('max_iter', 'lambda0', 'lambda_up', 'lambda_down', 'ftol', 'xtol', 'max_step', 'trace', 'lazy_jacobian', 'algorithm',
              'factor')
@@ -27,12 +29,8 @@ def param_indices(project, params, q):
         return np.arange(q)
     out = []
     for it in params:
-        if isinstance(it, (tuple, list)) and len(it) == 2 and isinstance(it[0], str):
-            try:
-                found = project.get_param_index(it[0], it[1])
-            except (KeyError, TypeError):
-                raise ValueError("params: the project has no parameter %r / %r" % (it[0], it[1])) from None
-            out += list(found.values()) if isinstance(found, dict) else [found]
+        if is_param_pair(it):
+            out += param_pair_indices(project, it, 'params')
         else:
             out.append(int(it))
     idx = np.asarray(out, dtype=np.int64)
