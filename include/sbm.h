@@ -459,6 +459,37 @@ int sbm_lm_trust_step_held(sbm_ctx* ctx, const double* J_dev, const double* r_de
                            const double* theta_dev, double* trial_dev, double* delta_dev, double* pred_dev,
                            double* dxnorm_dev, double* gtx_dev, int32_t* status_dev, const int32_t* held_dev);
 
+/* sbm_lm_trust_step_held inside a box: lower <= theta <= upper per vector and parameter (project/fitting.py `bounds=`).
+ * An added export: SBM_ABI_VERSION is unchanged.  An active-set method on top of the held step, the set chosen per call:
+ *   held [V][q]        nullable (nothing held by the caller)
+ *   lower, upper [V][q]          -inf / +inf: no bound on that side.  theta and trial are needed here.
+ *   active_out [V][q]  nullable  out: 0 free, 1 held by the caller, 2 held at its lower bound, 3 held at its upper bound
+ * 1. g_c = sum_m row_scale[m] J[m][c] r[m] for every column the caller has not held, one fma chain over the rows in
+ *    ascending order: bit for bit the g the normal equations produce for the column afterwards.
+ * 2. A column is bound-active at lower if theta_c <= lower_c and g_c > 0, at upper if theta_c >= upper_c and g_c < 0
+ *    (g_c == 0 leaves it free); free columns are those neither held nor bound-active.
+ * 3. The step is sbm_lm_trust_step_held's on that mask -- the same arithmetic in the same order.  Non-free columns get
+ *    dscale = 0, delta = 0, trial = theta (a copy); a column that leaves the active set therefore starts its
+ *    running-maximum scaling again from its current norm, and ||D theta|| is that of the reduced problem.
+ * 4. After the max_step clip every free component is projected: t = min(max(theta_c + x_c, lower_c), upper_c); where
+ *    t != theta_c + x_c, x_c = t - theta_c and trial_c = t (the bound's bits, not theta + x), and pred, dxnorm and gtx
+ *    are those of the step taken (as for a clipped step).  Unprojected components are written as the held kernel
+ *    writes them.  The clipped columns are not added to the active set and the system solved again.
+ * 5. A projected step that is no descent step of the model (not gtx < 0 and pred > 0): status 4, delta = 0,
+ *    trial = theta, pred = dxnorm = gtx = 0, lambda kept.  sbm_lm_update halves the radius on it, and as the radius
+ *    shrinks the step turns into a scaled gradient step whose projection descends; each such call is one spent
+ *    iteration (docs/history.md has counts).
+ * 6. Nothing free although the caller has not held everything -- a constrained stationary point: status 3, everything
+ *    else as for a vector with no free parameter (status 2).  sbm_lm_update marks such a start done.
+ * With infinite bounds and held = NULL the outputs are sbm_lm_trust_step_ex's.  Cost beside the held step: one more
+ * read of J (M dependent fmas on q of the 256 threads).  LDS as for sbm_lm_trust_step_held. */
+int sbm_lm_trust_step_bounded(sbm_ctx* ctx, const double* J_dev, const double* r_dev, double* dscale_dev,
+                              const double* radius_dev, double* lambda_dev, int32_t V, int32_t M, int32_t q,
+                              const double* row_scale_dev, const int32_t* skip_dev, double max_step,
+                              const double* theta_dev, double* trial_dev, double* delta_dev, double* pred_dev,
+                              double* dxnorm_dev, double* gtx_dev, int32_t* status_dev, const int32_t* held_dev,
+                              const double* lower_dev, const double* upper_dev, int32_t* active_out_dev);
+
 /* lmder's bookkeeping between two steps (MINPACK lmder.f, the loop around lmpar: what scipy.optimize.leastsq -- the
  * reference's optimiser, tests/test_Project.py:202-213, 351-357 -- does after every function evaluation), for V starts
  * in one launch: actual and predicted relative reduction, their ratio, the radius / lambda update (ratio <= 1/4: shrink
@@ -467,7 +498,8 @@ int sbm_lm_trust_step_held(sbm_ctx* ctx, const double* J_dev, const double* r_de
  * ratio <= 2; info 2: Delta <= xtol ||D theta||).  With |r|^2 = 2 cost lmder's quantities are prered = pred / cost,
  * dirder = gtx / (2 cost), actred = 1 - cost_trial / cost (-1 where 0.1 |r_trial| >= |r| or the trial point is unusable).
  * Where this departs from lmder.f, on purpose: a step status != 0 halves Delta, keeps lambda and the point and tests no
- * convergence; cost = 0 is divided by 1; pred <= 0 (possible for a clipped step only; lmder's prered is a sum of squares)
+ * convergence -- except status 3 (sbm_lm_trust_step_bounded: a constrained stationary point), which sets done = 1 and
+ * n_iter = iteration + 1, takes no point, leaves Delta alone and does not count the start as running; cost = 0 is divided by 1; pred <= 0 (possible for a clipped step only; lmder's prered is a sum of squares)
  * gives ratio 0 like lmder's prered = 0, so that no uphill step is taken; and ||D theta|| of info 2 is that of the
  * current point, before sbm_lm_accept moves it (lmder measures the point the iteration ends on).
  *   cost [V]            0.5 |r|^2 at the current points       norms_trial, status_trial [V]   |r|^2 and integration

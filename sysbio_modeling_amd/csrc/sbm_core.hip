@@ -10,7 +10,7 @@
 //                     loss_functions/squared_loss/squared_loss_function.py:27-80;
 //                     linear_scale_factor.py:27-42)
 // and the host side -- argument checks, LDS sizes, launches (launch_lds) -- of the kernels kept in headers of their own:
-//   sbm_lm.hpp              k_lm_step, k_lm_trust[_held], k_lm_update, k_lm_accept: the fitting loop (batched Levenberg-Marquardt
+//   sbm_lm.hpp              k_lm_step, k_lm_trust[_held|_bounded], k_lm_update, k_lm_accept: the fitting loop (batched Levenberg-Marquardt
 //                           step, lmder's trust-region step and bookkeeping)
 //   sbm_sampler.hpp         k_sf_entropy, k_mh_propose, k_mh_accept, k_mh_accept_hastings: scale-factor entropy integrals
 //                           (linear_scale_factor.py:63-81; the quadrature rule: sbm_sf_quadrature.hpp), candidate move and
@@ -1343,19 +1343,21 @@ extern "C" int sbm_lm_step(sbm_ctx* ctx, const double* J, const double* r, const
 // LDS); otherwise k_lm_trust_held, whose whole static LDS (LM_HELD_STATIC_LDS = 576 bytes: the same 304 + the list of free
 // columns and the waves' counts) is taken off the limit the row tile is chosen for, so that dynamic + static fit the
 // workgroup at every q.  The tile decides how many rows are staged at once, not the order of any sum.
+// bounds != NULL: k_lm_trust_bounded (held nullable, the same static LDS as k_lm_trust_held).
 static int lm_trust_launch(sbm_ctx* ctx, const double* J, const double* r, double* dscale, const double* radius, double* lambda,
                            int32_t V, int32_t M, int32_t q, const double* row_scale, const int32_t* skip, double max_step,
                            const double* theta, double* trial, double* delta, double* pred, double* dxnorm, double* gtx,
-                           int32_t* status, const int32_t* held) {
+                           int32_t* status, const int32_t* held, const LmBounds* bounds = nullptr) {
   if (!ctx || !J || !r || !dscale || !radius || !lambda || !delta || !pred || !dxnorm || !status)
     return sbm_fail(SBM_E_ARG, "sbm_lm_trust_step: NULL argument");
   if (V < 0 || M <= 0 || q <= 0 || q > LM_MAX_Q) return sbm_fail(SBM_E_ARG, "sbm_lm_trust_step: bad sizes V=%d M=%d q=%d (q <= %d)", V, M, q, LM_MAX_Q);
   if ((theta == nullptr) != (trial == nullptr)) return sbm_fail(SBM_E_ARG, "sbm_lm_trust_step_ex: theta and trial go together");
   if (V == 0) return 0;
   int tile = 0;
-  const size_t lds = lm_lds_bytes(q, 5, (size_t)lm_lds_limit(ctx) - (held ? LM_HELD_STATIC_LDS : 0), &tile);
+  const size_t lds = lm_lds_bytes(q, 5, (size_t)lm_lds_limit(ctx) - (held || bounds ? LM_HELD_STATIC_LDS : 0), &tile);
   if (!lds) return sbm_fail(SBM_E_ARG, "sbm_lm_trust_step: q = %d does not fit the %d KB of LDS of a workgroup", q, lm_lds_limit(ctx) / 1024);
   LmTrustArgs a{J, r, dscale, radius, lambda, delta, pred, dxnorm, status, M, q, tile, row_scale, skip, max_step, gtx, theta, trial};
+  if (bounds) return launch_lds(ctx, k_lm_trust_bounded, dim3(V), dim3(256), lds, a, held, *bounds);
   if (held) return launch_lds(ctx, k_lm_trust_held, dim3(V), dim3(256), lds, a, held);
   return launch_lds(ctx, k_lm_trust, dim3(V), dim3(256), lds, a);
 }
@@ -1374,6 +1376,18 @@ extern "C" int sbm_lm_trust_step_held(sbm_ctx* ctx, const double* J, const doubl
                                       double* pred, double* dxnorm, double* gtx, int32_t* status, const int32_t* held) {
   return lm_trust_launch(ctx, J, r, dscale, radius, lambda, V, M, q, row_scale, skip, max_step, theta, trial, delta, pred, dxnorm,
                          gtx, status, held);
+}
+
+extern "C" int sbm_lm_trust_step_bounded(sbm_ctx* ctx, const double* J, const double* r, double* dscale, const double* radius,
+                                         double* lambda, int32_t V, int32_t M, int32_t q, const double* row_scale,
+                                         const int32_t* skip, double max_step, const double* theta, double* trial,
+                                         double* delta, double* pred, double* dxnorm, double* gtx, int32_t* status,
+                                         const int32_t* held, const double* lower, const double* upper, int32_t* active_out) {
+  if (!theta || !trial || !lower || !upper)
+    return sbm_fail(SBM_E_ARG, "sbm_lm_trust_step_bounded: theta, trial, lower and upper are needed");
+  const LmBounds bounds{lower, upper, active_out};
+  return lm_trust_launch(ctx, J, r, dscale, radius, lambda, V, M, q, row_scale, skip, max_step, theta, trial, delta, pred, dxnorm,
+                         gtx, status, held, &bounds);
 }
 
 extern "C" int sbm_lm_trust_step(sbm_ctx* ctx, const double* J, const double* r, double* dscale, const double* radius,

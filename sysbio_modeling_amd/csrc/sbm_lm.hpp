@@ -1,4 +1,4 @@
-// sbm_lm.hpp -- kernels of the fitting loop (include/sbm.h: sbm_lm_step, sbm_lm_trust_step[_ex|_held], sbm_lm_update,
+// sbm_lm.hpp -- kernels of the fitting loop (include/sbm.h: sbm_lm_step, sbm_lm_trust_step[_ex|_held|_bounded], sbm_lm_update,
 // sbm_lm_accept).  The two step kernels share the builder of the normal equations (lm_normal_equations) and the
 // factorisation (lm_cholesky / lm_forward / lm_backward); the host wrappers with the argument checks are in sbm_core.hip.
 #ifndef SBM_LM_HPP
@@ -237,25 +237,80 @@ struct LmTrustArgs {
 // k_lm_update and k_lm_accept need no change for this: k_lm_update reads dscale only in ||D theta|| (exact zeros from
 // the held columns: lmder's xnorm of the reduced problem) and everything else per start; k_lm_accept copies trial rows,
 // whose held entries are theta's.
-template <bool HELD>
-__device__ __forceinline__ void lm_trust_body(LmTrustArgs a, const int32_t* held) {
+//
+// BOUNDED (with HELD; sbm_lm_trust_step_bounded): an active-set step inside the box lower <= theta <= upper.  The mask the
+// system is compacted by is chosen HERE, per call: a gradient pre-pass gives thread c < qf its g_c = sum_m rs_m J_mc r_m
+// (one fma chain over the rows in ascending order -- the chain lm_normal_equations runs for the column afterwards, so the
+// sign tested is the sign of the g the step uses), and a column that sits on a bound with the gradient pushing outward
+// (theta <= lower and g > 0, theta >= upper and g < 0) joins the caller's held ones for this step; g == 0 leaves it free.
+// From the ballot on, the kernel is the HELD kernel on that effective mask, with two additions after the max_step clip:
+// the step is projected into the box (a component that would leave it ends ON the bound: trial gets the bound's bits, and
+// the step counts as clipped, so pred, dxnorm and gtx are those of the step taken), and a projected step that is no
+// descent step of the model any more (not gtx < 0 and pred > 0) is not taken (status 4: k_lm_update halves the radius).
+// Nothing free although the caller has not held everything: a constrained stationary point, status 3.
+struct LmBounds {
+  const double* lower;   // [V][q]  -inf: no bound on that side
+  const double* upper;   // [V][q]  +inf
+  int32_t* active_out;   // [V][q]  nullable: 0 free, 1 held by the caller, 2 held at the lower bound, 3 at the upper
+};
+
+template <bool HELD, bool BOUNDED = false>
+__device__ __forceinline__ void lm_trust_body(LmTrustArgs a, const int32_t* held, LmBounds b = LmBounds{}) {
+  static_assert(HELD || !BOUNDED, "the bounded step compacts its system");
   extern __shared__ __attribute__((aligned(16))) double lm_smem[];
   const int v = blockIdx.x, tid = threadIdx.x, qf = a.q, M = a.M, TILE = a.tile;
-  auto leave_alone = [&]() {                 // a skipped vector, or one with no free column: no step, status 2
+  // no step: delta = 0, trial = theta.  Status 2: a skipped vector, or one with no free column; 1: no system solved;
+  // 3, 4: see BOUNDED
+  auto leave_alone = [&](int status) {
     for (int c = tid; c < qf; c += 256) {
       a.delta[(size_t)v * qf + c] = 0.0;
       if (a.trial && a.theta) a.trial[(size_t)v * qf + c] = a.theta[(size_t)v * qf + c];
     }
-    if (tid == 0) { a.pred[v] = 0.0; a.dxnorm[v] = 0.0; a.status[v] = 2; if (a.gtx) a.gtx[v] = 0.0; }
+    if (tid == 0) { a.pred[v] = 0.0; a.dxnorm[v] = 0.0; a.status[v] = status; if (a.gtx) a.gtx[v] = 0.0; }
   };
   int q = qf;                                // columns of the system that is solved
   [[maybe_unused]] const short* idx = nullptr;
   if constexpr (HELD) {
-    if (a.skip && a.skip[v]) { leave_alone(); return; }
+    if (a.skip && a.skip[v]) { leave_alone(2); return; }
     // the free columns in ascending order: a ballot per wave (qf <= 128: waves 0 and 1 have columns), the waves' counts in LDS
     __shared__ short s_idx[LM_MAX_Q];
     __shared__ int s_cnt[4];
-    const bool is_free = tid < qf && held[(size_t)v * qf + tid] == 0;
+    [[maybe_unused]] int code = 0;           // BOUNDED: this thread's column as active_out names it
+    bool is_free;
+    if constexpr (BOUNDED) {
+      if (tid < qf) {
+        const size_t at = (size_t)v * qf + tid;
+        if (held && held[at] != 0) {
+          code = 1;
+        } else {
+          const double* Jc = a.J + (size_t)v * M * qf + tid;
+          const double* rv = a.r + (size_t)v * M;
+          // one chain of M dependent fmas; the loads of eight rows are issued together, ahead of their fmas (the order of the
+          // chain, and so its bits, is the rows')
+          double gc = 0.0;
+          for (int m0 = 0; m0 < M; m0 += 8) {
+            double val[8], rr[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+              const int m = min(m0 + k, M - 1);
+              val[k] = Jc[(size_t)m * qf];
+              if (a.row_scale) val[k] *= a.row_scale[m];
+              rr[k] = rv[m];
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+              if (m0 + k < M) gc = fma(val[k], rr[k], gc);
+          }
+          const double th = a.theta[at];
+          if (th <= b.lower[at] && gc > 0.0) code = 2;
+          else if (th >= b.upper[at] && gc < 0.0) code = 3;
+        }
+        if (b.active_out) b.active_out[at] = code;
+      }
+      is_free = tid < qf && code == 0;
+    } else {
+      is_free = tid < qf && held[(size_t)v * qf + tid] == 0;
+    }
     const unsigned long long m = __ballot(is_free);
     const int lane = tid & 63, wave = tid >> 6;
     if (lane == 0) s_cnt[wave] = __popcll(m);
@@ -265,7 +320,13 @@ __device__ __forceinline__ void lm_trust_body(LmTrustArgs a, const int32_t* held
     q = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
     if (is_free) s_idx[base + __popcll(m & ((1ull << lane) - 1ull))] = (short)tid;
     if (tid < qf && !is_free) a.dscale[(size_t)v * qf + tid] = 0.0;
-    if (q == 0) { leave_alone(); return; }   // (uniform)
+    if (q == 0) {                            // (uniform)
+      if constexpr (BOUNDED) {
+        if (__syncthreads_or(code >= 2)) { leave_alone(3); return; }      // bounds hold what the caller left free
+      }
+      leave_alone(2);
+      return;
+    }
     if (tid < qf && !is_free) {
       a.delta[(size_t)v * qf + tid] = 0.0;
       if (a.trial && a.theta) a.trial[(size_t)v * qf + tid] = a.theta[(size_t)v * qf + tid];
@@ -286,7 +347,7 @@ __device__ __forceinline__ void lm_trust_body(LmTrustArgs a, const int32_t* held
   __shared__ int s_bad;
   __shared__ double s_red[4];
   if constexpr (!HELD)
-    if (a.skip && a.skip[v]) { leave_alone(); return; }
+    if (a.skip && a.skip[v]) { leave_alone(2); return; }
   if (tid == 0) s_bad = 0;
   LmTriangle n;
   int n_own;
@@ -381,20 +442,26 @@ __device__ __forceinline__ void lm_trust_body(LmTrustArgs a, const int32_t* held
       __syncthreads();
     }
   }
-  if (bad || !have) {
-    for (int c = tid; c < qf; c += 256) {
-      a.delta[(size_t)v * qf + c] = 0.0;
-      if (a.trial && a.theta) a.trial[(size_t)v * qf + c] = a.theta[(size_t)v * qf + c];
-    }
-    if (tid == 0) { a.pred[v] = 0.0; a.dxnorm[v] = 0.0; a.status[v] = 1; if (a.gtx) a.gtx[v] = 0.0; }
-    return;
-  }
+  if (bad || !have) { leave_alone(1); return; }
   // a step bound per component (exp(theta) has to stay finite): clip, and report the quantities of the step TAKEN
   bool clipped = false;
   if (a.max_step > 0.0) {
     int cl = 0;
     if (tid < q && fabs(x[tid]) > a.max_step) { x[tid] = copysign(a.max_step, x[tid]); cl = 1; }
     clipped = __syncthreads_or(cl) != 0;
+  }
+  // BOUNDED: the projection into the box; a component that would leave it ends on the bound itself
+  [[maybe_unused]] bool projected = false, on_bound = false;
+  [[maybe_unused]] double t_bound = 0.0;
+  if constexpr (BOUNDED) {
+    if (tid < q) {
+      const size_t at = (size_t)v * qf + col(tid);
+      const double th = a.theta[at], s = th + x[tid];
+      const double t = fmin(fmax(s, b.lower[at]), b.upper[at]);
+      if (t != s) { x[tid] = t - th; t_bound = t; on_bound = true; }
+    }
+    projected = __syncthreads_or(on_bound ? 1 : 0) != 0;
+    clipped = clipped || projected;
   }
   double gx = 0.0;
   if (tid < q) gx = g[tid] * x[tid];
@@ -411,9 +478,15 @@ __device__ __forceinline__ void lm_trust_body(LmTrustArgs a, const int32_t* held
     for (int k = 0; k < n_own; ++k) xhx += (n.oi[k] == n.oj[k] ? 1.0 : 2.0) * n.acc[k] * x[n.oi[k]] * x[n.oj[k]];
     tot = -gtx - 0.5 * block_sum(xhx, s_red);
   }
+  if constexpr (BOUNDED) {
+    // (uniform: gtx and tot are block sums.)  lmder's radius formula wants g . x < 0; with the radius halved often enough
+    // the step is a scaled gradient step, whose projection descends
+    if (projected && !(gtx < 0.0 && tot > 0.0)) { leave_alone(4); return; }
+  }
   if (tid < q) {
     a.delta[(size_t)v * qf + col(tid)] = x[tid];
-    if (a.trial && a.theta) a.trial[(size_t)v * qf + col(tid)] = a.theta[(size_t)v * qf + col(tid)] + x[tid];
+    if (a.trial && a.theta)
+      a.trial[(size_t)v * qf + col(tid)] = (BOUNDED && on_bound) ? t_bound : a.theta[(size_t)v * qf + col(tid)] + x[tid];
   }
   if (tid == 0) { a.pred[v] = tot; a.dxnorm[v] = dxn; a.lambda[v] = lam; a.status[v] = 0; if (a.gtx) a.gtx[v] = gtx; }
 }
@@ -423,6 +496,11 @@ __global__ void __launch_bounds__(256) k_lm_trust(LmTrustArgs a) { lm_trust_body
 // waves' counts = LM_HELD_STATIC_LDS, which the host wrapper takes off the limit it chooses the row tile for.
 constexpr int LM_HELD_STATIC_LDS = 576;
 __global__ void __launch_bounds__(256) k_lm_trust_held(LmTrustArgs a, const int32_t* held) { lm_trust_body<true>(a, held); }
+// held nullable here; theta, trial, lower, upper are not.  The same static LDS as k_lm_trust_held (the gradient pre-pass and
+// the projection live in registers): LM_HELD_STATIC_LDS serves both.
+__global__ void __launch_bounds__(256) k_lm_trust_bounded(LmTrustArgs a, const int32_t* held, LmBounds b) {
+  lm_trust_body<true, true>(a, held, b);
+}
 
 // ---------------------------------------------------------------------------------------------
 // sbm_lm_update / sbm_lm_accept: lmder's bookkeeping between two trust-region steps, for V starts in two launches
@@ -435,7 +513,7 @@ struct LmUpdateArgs {
   const double* pred;       // [V] from sbm_lm_trust_step_ex
   const double* dxnorm;     // [V]
   const double* gtx;        // [V]
-  const int32_t* st;        // [V] status of the trust step (0 ok, 1 no system solved, 2 skipped)
+  const int32_t* st;        // [V] status of the trust step (0 ok, 1 no system solved, 2 skipped, 3 / 4: sbm_lm_trust_step_bounded)
   const double* theta;      // [V][q] current point (for ||D theta||)
   const double* dscale;     // [V][q]
   double* radius;           // [V] in / out
@@ -469,8 +547,15 @@ __global__ void __launch_bounds__(256) k_lm_update(LmUpdateArgs a) {
   const double dirder = a.gtx[v] / (2.0 * safe);               // g . p / |r|^2 (= -(|J p|^2 + lam |D p|^2) / |r|^2 for an unclipped step)
   const double ratio = prered > 0.0 ? actred / prered : 0.0;
   if (a.ratio_out) a.ratio_out[v] = ratio;
+  if (st == 3) {
+    // sbm_lm_trust_step_bounded: every parameter the caller left free sits on a bound with the gradient pushing outward --
+    // a constrained stationary point.  Converged where it stands; the radius is not touched
+    a.done[v] = 1;
+    a.n_iter[v] = a.iteration + 1;
+    return;
+  }
   if (st != 0) {
-    // no system could be solved: halve the radius, keep the point
+    // no system could be solved (1), or the projected step did not descend (4): halve the radius, keep the point
     a.radius[v] = 0.5 * radius;
     atomicAdd(a.counters, 1);
     return;

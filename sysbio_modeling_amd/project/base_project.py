@@ -875,7 +875,10 @@ class Project(object):
         """Multi-start Levenberg-Marquardt from every row of ``thetas0`` at once (project/fitting.py);
         the batched counterpart of ``leastsq(self.residuals, x0, Dfun=self.calc_project_jacobian)``.
         ``held=``: parameters that stay at their starting values -- a bool mask (q,) or (V, q), a list of indices, or a
-        list of ``(p_group, settings)`` pairs."""
+        list of ``(p_group, settings)`` pairs.
+        ``bounds=``: a box the fitted parameters stay in (log units, like ``thetas0``) -- ``(lower, upper)``, each a scalar,
+        (q,) or (V, q), or ``{(p_group, settings): (lo, hi)}``; the result gains 'at_bound' (V, q): -1 / 0 / +1.  Held
+        parameters are exempt; starts must lie inside the box."""
         from .fitting import levenberg_marquardt_batch
         return levenberg_marquardt_batch(self, thetas0, **options)
 

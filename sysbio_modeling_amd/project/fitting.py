@@ -112,6 +112,64 @@ def normalize_held(held, V, q, project=None):
     return np.ascontiguousarray(np.broadcast_to(mask, (V, q)))
 
 
+def _bound_array(x, V, q, what):
+    """One side of ``bounds`` as a (V, q) array: a scalar, (q,) or (V, q)"""
+    if hasattr(x, 'detach'):
+        x = x.detach().cpu().numpy()
+    try:
+        arr = np.asarray(x, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("bounds: %s is a scalar or an array (q,) or (V, q)" % what) from None
+    if arr.shape not in ((), (q,), (V, q)):
+        raise ValueError("bounds: %s has shape %s; a scalar, (q,) = (%d,) or (V, q) = (%d, %d)" % (what, arr.shape, q, V, q))
+    return np.array(np.broadcast_to(arr, (V, q)), dtype=np.float64, order='C')
+
+
+def normalize_bounds(bounds, V, q, project=None, thetas0=None, held=None):
+    """The ``bounds`` argument of ``fit_batch`` as two contiguous (V, q) float64 arrays (lower, upper), in the units of
+    ``thetas0`` (log parameters); an infinite entry leaves that side open.  Accepted: ``(lower, upper)``, each a scalar, an
+    array (q,) or (V, q); or a dict ``{(p_group, settings): (lo, hi)}`` resolved with ``project.get_param_index`` (every
+    setting of the group with 'all'), parameters it does not name being unbounded.  ``held`` (V, q) bool: held columns are
+    exempt from bounds altogether and come back unbounded.  ``thetas0`` (V, q): a start outside its box in a column that is
+    not held is refused (scipy's "x0 is infeasible").  ValueError also on a wrong shape, a NaN, lower > upper anywhere and
+    a name the project does not know."""
+    if isinstance(bounds, dict):
+        if project is None:
+            raise ValueError("bounds: (p_group, settings) names need the project that resolves them")
+        lower, upper = np.full((V, q), -np.inf), np.full((V, q), np.inf)
+        for pair, lo_hi in bounds.items():
+            if not is_param_pair(pair):
+                raise ValueError("bounds: the keys of a dict are (p_group, settings) pairs, not %r" % (pair,))
+            try:
+                lo, hi = (float(x) for x in lo_hi)
+            except (TypeError, ValueError):
+                raise ValueError("bounds: the value of %r is a pair (lo, hi) of numbers" % (pair,)) from None
+            for c in param_pair_indices(project, pair, 'bounds'):
+                lower[:, c], upper[:, c] = lo, hi
+    else:
+        try:
+            lo, hi = bounds
+        except (TypeError, ValueError):
+            raise ValueError("bounds: a pair (lower, upper) or a dict {(p_group, settings): (lo, hi)}") from None
+        lower, upper = _bound_array(lo, V, q, 'lower'), _bound_array(hi, V, q, 'upper')
+    if np.isnan(lower).any() or np.isnan(upper).any():
+        raise ValueError("bounds: NaN among the bounds")
+    if held is not None:
+        held = np.asarray(held, dtype=bool)
+        lower[held], upper[held] = -np.inf, np.inf
+    if (lower > upper).any():
+        v, c = np.argwhere(lower > upper)[0]
+        raise ValueError("bounds: lower > upper (start %d, parameter %d: %r > %r)" % (v, c, lower[v, c], upper[v, c]))
+    if thetas0 is not None:
+        x0 = np.asarray(thetas0, dtype=np.float64).reshape(V, q)
+        outside = (x0 < lower) | (x0 > upper)
+        if outside.any():
+            v, c = np.argwhere(outside)[0]
+            raise ValueError("bounds: the start is infeasible (start %d, parameter %d: %r outside [%r, %r]); clip the starts "
+                             "into the box first" % (v, c, x0[v, c], lower[v, c], upper[v, c]))
+    return lower, upper
+
+
 def _prepare(project, thetas0, lazy_jacobian):
     """What the three loops below begin with: the refusal of prior rows under ``reference_compat``, ``lazy_jacobian`` resolved,
     the library and the context (device, stream) the project's model lives on, and the starts staged on the device as a copy
@@ -207,7 +265,7 @@ def _median_over(live):
     return lambda t: float(t[live].median()) if some else 0.0
 
 
-def _result(th, cost, n_iter, done, n_eval, n_jac, history=None, held=None):
+def _result(th, cost, n_iter, done, n_eval, n_jac, history=None, held=None, bounds=None):
     """The dict `levenberg_marquardt_batch` returns, from the loop's device tensors"""
     import torch
     out = {'theta': th.cpu().numpy(), 'cost': cost.cpu().numpy(), 'n_iter': n_iter.cpu().numpy().astype(np.int64),
@@ -215,6 +273,9 @@ def _result(th, cost, n_iter, done, n_eval, n_jac, history=None, held=None):
            'n_jacobian_evaluations': n_jac}
     if held is not None:
         out['held'] = held
+    if bounds is not None:
+        lower, upper = bounds
+        out['at_bound'] = (out['theta'] == upper).astype(np.int8) - ((out['theta'] == lower) & (lower < upper)).astype(np.int8)
     if history is not None:
         out['history'] = history
     return out
@@ -222,7 +283,7 @@ def _result(th, cost, n_iter, done, n_eval, n_jac, history=None, held=None):
 
 def levenberg_marquardt_batch(project, thetas0, max_iter=60, lambda0=1e-2, lambda_up=4.0, lambda_down=3.0,
                               ftol=1.49012e-8, xtol=1.49012e-8, max_step=2.0, trace=False, lazy_jacobian='auto',
-                              algorithm='trust_region', factor=100.0, held=None, **integrator_overrides):
+                              algorithm='trust_region', factor=100.0, held=None, bounds=None, **integrator_overrides):
     """Minimise 0.5 |r(theta)|^2 from every row of ``thetas0`` (V, q), independently.
 
     ``algorithm='trust_region'`` (default since round 2): MINPACK's lmder, batched (`_trust_region_batch` below) -- the
@@ -264,12 +325,24 @@ def levenberg_marquardt_batch(project, thetas0, max_iter=60, lambda0=1e-2, lambd
     with nothing free comes back as it came, converged.  Supported with ``algorithm='trust_region'`` and an integration
     that is one device call; ``held=None`` is the loop as it was.
 
+    ``bounds``: a box the fitted parameters stay in, in the units of ``thetas0`` (log parameters) -- ``(lower, upper)``, each
+    a scalar, an array (q,) or (V, q), infinite where a side is open; or a dict ``{(p_group, settings): (lo, hi)}`` whose
+    unnamed parameters are unbounded (`normalize_bounds`).  Held parameters are exempt; a start outside its box is refused
+    (clip the starts first), as scipy's ``least_squares`` refuses an infeasible x0.  The cost function is unchanged (a prior
+    changes it): every step is an active-set step of ``sbm_lm_trust_step_bounded`` -- a parameter on a bound with the
+    gradient pushing outward is held for that step, the step on the others is lmder's and is projected into the box, so an
+    iterate that reaches a bound lies ON it bit for bit.  A projected step that no longer descends in the model is not taken
+    and costs that iteration (the radius is halved); a start whose free parameters all sit on bounds with the gradient
+    pushing outward has converged.  Same support as ``held``; ``bounds=None`` is the loop as it was, the same entry points
+    included.
+
     With a handful of starts the chip is mostly empty: ``variant='small_batch'`` (an integrator override) lets the
     sensitivity kernel use its small-batch split while starts x experiments x chunks <= 2048.
 
     Returns a dict of numpy arrays: theta (V, q), cost (V,) = 0.5 |r|^2, n_iter (V,) iterations until
     convergence (max_iter if never), converged (V,) bool, n_evaluations (total trial points integrated),
-    n_jacobian_evaluations (those integrated with sensitivities); with ``held``, 'held' (V, q) bool; with
+    n_jacobian_evaluations (those integrated with sensitivities); with ``held``, 'held' (V, q) bool; with ``bounds``,
+    'at_bound' (V, q) int8: -1 / +1 where the returned theta equals its lower / upper bound, else 0; with
     ``trace=True`` also 'history': per iteration the number of accepted steps, starts still running, median cost,
     damping, relative decrease and largest step component (costs a device synchronisation per iteration).
     """
@@ -277,15 +350,16 @@ def levenberg_marquardt_batch(project, thetas0, max_iter=60, lambda0=1e-2, lambd
     # ONE device call; the control loops of _control.py (method='auto', 'implicit_romberg') and algorithm='trust_region_torch'
     # (round 2's spelling in tensor selects, kept as the cross-check) take the other
     fused = algorithm in ('trust_region', 'lmder', 'minpack') and one_device_call(project, integrator_overrides)
-    if held is not None and not fused:
-        raise ValueError("fit_batch: held parameters are supported by algorithm='trust_region' with an integration method "
+    if (held is not None or bounds is not None) and not fused:
+        raise ValueError("fit_batch: %s are supported by algorithm='trust_region' with an integration method "
                          "that is one device call (not method='auto' / the host-controlled implicit methods); got "
-                         "algorithm=%r, method=%r" % (algorithm, project._options(**integrator_overrides).get('method')))
+                         "algorithm=%r, method=%r" % ('held parameters' if held is not None else 'bounds', algorithm,
+                                                      project._options(**integrator_overrides).get('method')))
     if algorithm in ('trust_region', 'lmder', 'minpack', 'trust_region_torch'):
         fit = dict(max_iter=max_iter, ftol=ftol, xtol=xtol, factor=factor, trace=trace, lazy_jacobian=lazy_jacobian,
                    max_step=max_step)
         if fused:
-            return _trust_region_fused(project, thetas0, held=held, **fit, **integrator_overrides)
+            return _trust_region_fused(project, thetas0, held=held, bounds=bounds, **fit, **integrator_overrides)
         return _trust_region_batch(project, thetas0, **fit, **integrator_overrides)
     if algorithm != 'marquardt':
         raise ValueError("fit_batch: unknown algorithm %r ('marquardt', 'trust_region' or 'trust_region_torch')" % (algorithm,))
@@ -465,7 +539,7 @@ def _trust_region_batch(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
 
 
 def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.49012e-8, factor=100.0, trace=False,
-                        lazy_jacobian='auto', max_step=2.0, held=None, **integrator_overrides):
+                        lazy_jacobian='auto', max_step=2.0, held=None, bounds=None, **integrator_overrides):
     """`_trust_region_batch` with the bookkeeping on the device: per iteration ONE ``sbm_lm_trust_step_ex`` (lmpar, the
     clipped step and the trial point), the integration of the trial points (``sbm_jacobian_batch`` /
     ``sbm_residuals_batch`` into preallocated buffers), ONE ``sbm_lm_update`` (lmder's ratio / radius / acceptance /
@@ -476,13 +550,21 @@ def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
     ``held`` (see `levenberg_marquardt_batch`): the step comes from ``sbm_lm_trust_step_held`` with the (V, q) mask, the
     initial radius factor * ||D theta|| is that of the free parameters, and a start with nothing free is done before the
     first step.  ``sbm_lm_update`` and ``sbm_lm_accept`` are called as ever: held columns have dscale = 0 and
-    trial = theta."""
+    trial = theta.
+
+    ``bounds``: the step comes from ``sbm_lm_trust_step_bounded`` (with the held mask, or NULL), which chooses the active set
+    from this iteration's gradient on the device: no read-back is added.  Its status 3 (a constrained stationary point)
+    ends a start in ``sbm_lm_update``; its status 4 (a projected step that does not descend) halves the radius there."""
     import torch
     th, V, q, dev, lib, ctx, lazy_jacobian = _prepare(project, thetas0, lazy_jacobian)
     held_dev = None
     if held is not None:
         held = normalize_held(held, V, q, project)
         held_dev = torch.from_numpy(held).to(dev)
+    lower_dev = upper_dev = None
+    if bounds is not None:
+        bounds = normalize_bounds(bounds, V, q, project, thetas0=th.cpu().numpy(), held=held)
+        lower_dev, upper_dev = (torch.from_numpy(b).to(dev) for b in bounds)
     ev = DeviceEvaluator(project)
     M = ev.RT
     f64, i32 = torch.float64, torch.int32
@@ -526,7 +608,12 @@ def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
     history = []
     held_i32 = held_dev.to(i32).contiguous() if held_dev is not None else None
     for it in range(max_iter):
-        if held_i32 is None:
+        if lower_dev is not None:
+            _lib.check(lib.sbm_lm_trust_step_bounded(ctx.handle, p(cur_J), p(cur_r), p(dscale), p(radius), p(lam), V, M, q,
+                                                     p(row_scale), p(done), float(max_step), p(th), p(trial), p(delta), p(pred),
+                                                     p(dxnorm), p(gtx), p(st), p(held_i32), p(lower_dev), p(upper_dev), None),
+                       'sbm_lm_trust_step_bounded')
+        elif held_i32 is None:
             _lib.check(lib.sbm_lm_trust_step_ex(ctx.handle, p(cur_J), p(cur_r), p(dscale), p(radius), p(lam), V, M, q,
                                                 p(row_scale), p(done), float(max_step), p(th), p(trial), p(delta), p(pred),
                                                 p(dxnorm), p(gtx), p(st)), 'sbm_lm_trust_step_ex')
@@ -549,6 +636,9 @@ def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
             launch = dict(ms=1e3 * t_launch, steps_max=int(per.max()), steps_mean=float(per.double().mean()),
                           steps_p99=float(per.double().flatten().quantile(0.99)), failed=int((tr['status'] != 0).sum()),
                           done=int((done != 0).sum()))
+            if lower_dev is not None:
+                # steps the bounds took away: projected steps that did not descend (status 4), each a spent iteration
+                launch['no_descent'] = int(((st == 4) & (done == 0)).sum())
         cost_prev = cost.clone() if trace else None
         _lib.check(lib.sbm_lm_update(ctx.handle, p(cost), p(tr['norms']), p(tr['status']), p(pred), p(dxnorm), p(gtx), p(st),
                                      p(th), p(dscale), V, q, float(ftol), float(xtol), it, 1 if it == 0 else 0, p(radius),
@@ -589,4 +679,4 @@ def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
         if live == 0:
             break
     torch.cuda.synchronize(dev)
-    return _result(th, cost, n_iter, done, n_eval, n_jac, history if trace else None, held)
+    return _result(th, cost, n_iter, done, n_eval, n_jac, history if trace else None, held, bounds)

@@ -17,7 +17,7 @@ from .fitting import is_param_pair, param_pair_indices
 
 # what fit_batch itself consumes; everything else in **fit_options is an integrator override (method, rtol, ...)
 _FIT_KEYS = ('max_iter', 'lambda0', 'lambda_up', 'lambda_down', 'ftol', 'xtol', 'max_step', 'trace', 'lazy_jacobian', 'algorithm',
-             'factor')
+             'factor', 'bounds')
 
 
 def param_indices(project, params, q):
@@ -47,7 +47,10 @@ def profile_likelihood_batch(project, theta_hat, params='all', offsets=np.linspa
 
     ``offsets`` (K,), strictly increasing and positive, are used in both directions: parameter i is held at
     ``theta_hat[i] - offsets[k]`` and ``theta_hat[i] + offsets[k]`` while all the others are fitted
-    (``fit_batch(held=...)``; ``fit_options`` go there: max_iter, ftol, ..., integrator overrides).
+    (``fit_batch(held=...)``; ``fit_options`` go there: max_iter, ftol, ..., integrator overrides).  ``bounds=`` among them
+    keeps the fitted parameters in a box: a ``(lower, upper)`` pair of scalars or (q,) arrays, or a dict of
+    ``(p_group, settings)`` names, the same box for every branch; the profiled parameter, being held, is exempt from it,
+    and ``theta_hat`` has to lie inside.
 
     ``continuation=True``: the 2 P branches are the starts of one ``fit_batch`` call per grid step k; a branch starts from
     its own optimum of step k - 1 (``theta_hat`` at k = 0) -- K calls.  ``continuation=False``: all 2 P K points start from
