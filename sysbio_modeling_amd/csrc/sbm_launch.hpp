@@ -72,7 +72,9 @@ static bool sbm_iex_seq_enabled() {
   static const bool on = [] { const char* v = getenv("SBM_IEX_SEQ"); return !(v && v[0] == '0'); }();
   return on;
 }
-// developer switch: SBM_DEBUG_LAUNCH prints the shape of every persistent launch
+// developer switch: SBM_DEBUG_LAUNCH prints the shape of every persistent launch, and names the matrix-core and packed
+// sensitivity kernels with their compiled plan when a call runs them (a forced variant the launcher does not accept falls
+// through to the row kernels without a word: tests/test_gpu_tile_edges.py reads these lines)
 static bool sbm_debug_launch() {
   static const bool on = getenv("SBM_DEBUG_LAUNCH") != nullptr;
   return on;
@@ -181,6 +183,7 @@ static int sbm_launch_model(int kind, const sbm_kernel_args* args, hipStream_t s
         const hipError_t e = sbm_zero_report(a, stream);
         if (e != hipSuccess) return (int)e;
       }
+      if (sbm_debug_launch()) fprintf(stderr, "sbm_sens_mfma_kernel: RT %d CT %d NCH %d LDJ %d LDA %d, %d trajectories\n", SbmMfmaPlan<M>::RT, SbmMfmaPlan<M>::CT, nch, SbmMfmaShared<M, SbmMfmaPlan<M>::CT>::LDJ, SbmMfmaShared<M, SbmMfmaPlan<M>::CT>::LDA, a.n_traj);
       return sbm_with_method(a.opts.method, [&](auto m) {
         hipLaunchKernelGGL((sbm_sens_mfma_kernel<M, decltype(m)::value>), dim3(a.n_traj, nch), dim3(64), 0, stream, a);
         return (int)hipGetLastError();
@@ -196,6 +199,7 @@ static int sbm_launch_model(int kind, const sbm_kernel_args* args, hipStream_t s
     // trajectory alone in its wavefront costs what it costs in the unpacked kernels; the single-vector methods of the
     // Python classes ask for SMALL_BATCH and keep the row kernels' lower latency.
     if (kind == SBM_KIND_SENS && (a.opts.variant == SBM_VARIANT_PACKED || a.opts.variant == SBM_VARIANT_AUTO)) {
+      if (sbm_debug_launch()) fprintf(stderr, "sbm_sens_packed_kernel: SEG %d, %d trajectories, grid %d\n", SEG, a.n_traj, (a.n_traj + 64 / SEG - 1) / (64 / SEG));
       return sbm_with_method(a.opts.method, [&](auto m) {
         hipLaunchKernelGGL((sbm_sens_packed_kernel<M, decltype(m)::value, SEG>), dim3((a.n_traj + 64 / SEG - 1) / (64 / SEG)), dim3(64), 0, stream, a);
         return (int)hipGetLastError();

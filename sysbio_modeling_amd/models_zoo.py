@@ -207,6 +207,71 @@ def seq_layout_specs():
     return specs
 
 
+# ----------------------------------------------------------------------------
+# tile / segment edges of the MFMA and packed sensitivity kernels
+# ----------------------------------------------------------------------------
+# (n_vars, n_sens): sizes on both sides of every 16-row / 16-column tile boundary of sbm_sens_mfma_kernel and the 16- and
+# 32-lane segments of sbm_sens_packed_kernel (tests/test_tile_edge_layouts_cpu.py::EXPECTED says what each one reaches)
+TILE_EDGE_SHAPES = ((7, 16), (16, 15), (7, 32), (17, 14), (16, 17), (15, 33), (16, 49), (33, 17), (49, 17), (64, 16))
+
+
+def tile_edge_offsets(n):
+    """the four coupling offsets of ``tile_edge_spec``: with the diagonal, a non-zero in every 16 x 16 block of df/dy"""
+    return sorted(set(o for o in (1, n // 4 + 1, n // 2, n - 3) if 0 < o < n))
+
+
+def tile_edge_spec(n, n_cols, name=None):
+    """A sparse circulant network in the form of ``dense_spec`` with EXACTLY ``n_cols`` sensitivity columns:
+
+        x_i' = k_i u_i / (1 + u_i) - d_i x_i,
+        u_i = b_i + w_i x_{i+o0} + v_{i mod h} x_{i+o1} + (x_{i+o2} + x_{i+o3}) / 2      (indices mod n, h = ceil(n / 2)),
+
+    offsets ``tile_edge_offsets(n)``: five non-zeros per row of df/dy, at least one in every 16 x 16 block.  Up to five
+    parameters per row: production k_i, degradation d_i, basal input b_i and two coupling weights, of which v_j is SHARED
+    by the rows j and j + h -- a column with J_p entries in two row tiles, whatever the other columns of its tile are.
+    4 n + h parameters, laid out k, v, w, d, b, k, v, ... with the row index of every family stepping by g ~ n / 2
+    (coprime to n: consecutive columns of a family sit in different row tiles); the first ``n_cols`` are free, the rest
+    ``fixed``.  Every 16-column tile of the free ones, a last tile of one column included (position 16 is a v), then has
+    J_p entries in more than one row tile, and no column is structurally zero (the coupling graph is strongly
+    connected): tests/test_tile_edge_layouts_cpu.py asserts both."""
+    from math import gcd
+    h = (n + 1) // 2
+    if not 0 < n_cols <= 4 * n + h:
+        raise ValueError("tile_edge_spec(%d): 1 .. %d sensitivity columns" % (n, 4 * n + h))
+    offs = tile_edge_offsets(n)
+    if len(offs) != 4:
+        raise ValueError("tile_edge_spec: n = %d is too small for four distinct offsets" % n)
+    xs = [Symbol('x%d' % i) for i in range(n)]
+    fam = {f: [Symbol('%s%d' % (f, i)) for i in range(h if f == 'v' else n)] for f in 'kdbwv'}
+    eq = OrderedDict()
+    for i in range(n):
+        u = fam['b'][i] + fam['w'][i] * xs[(i + offs[0]) % n] + fam['v'][i % h] * xs[(i + offs[1]) % n] + \
+            sympy.Rational(1, 2) * (xs[(i + offs[2]) % n] + xs[(i + offs[3]) % n])
+        eq['x%d' % i] = fam['k'][i] * u / (1 + u) - fam['d'][i] * xs[i]
+    g = next(s for s in range(n // 2, n) if gcd(s, n) == 1)
+    taken = {f: 0 for f in 'kvwdb'}
+    params = []
+    while len(params) < 4 * n + h:
+        for f in 'kvwdb':
+            c = taken[f]
+            if c < len(fam[f]):
+                params.append(str(fam[f][c if f == 'v' else (c * g) % n]))
+                taken[f] = c + 1
+    return ModelSpec(name=name or 'tile%d_%d' % (n, n_cols), variables=[str(x) for x in xs], params=params, equations=eq,
+                     fixed=params[n_cols:])
+
+
+def tile_edge_specs():
+    """The models of tests/test_gpu_tile_edges.py, one per entry of TILE_EDGE_SHAPES (the list build() compiles)."""
+    return [tile_edge_spec(n, k) for n, k in TILE_EDGE_SHAPES]
+
+
+def tile_edge_ensemble(spec, n_vectors, seed=5):
+    """(V, n_params) parameter vectors of a tile-edge model, every parameter log-uniform in [0.3, 1.5]"""
+    rng = np.random.default_rng(seed)
+    return np.exp(rng.uniform(np.log(0.3), np.log(1.5), (n_vectors, len(spec.params))))
+
+
 def stiff_nominal_params(n=50):
     a = 10.0 ** np.linspace(0.0, 6.0, n)
     b = 0.5 * np.ones(n)

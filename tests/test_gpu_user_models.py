@@ -440,7 +440,10 @@ def test_random_networks_all_variants(seed, n):
     t = np.linspace(0, 20.0, 1000)
     idx = np.array([0, 333, 999])
     ref = [_odeint_ref(gm, P[v], t) for v in (0, 3)]
-    for variant in ('per_wave', 'row_lane', 'row_group'):
+    # 'auto' on the two small networks: rand6_1 (13 columns) runs sbm_sens_packed_kernel, 16 lanes per trajectory; rand11_2
+    # (24 columns, 11 x 25 = 275 entries: over the packed kernel's 256) whatever row kernel the launcher picks
+    # (tests/test_tile_edge_layouts_cpu.py::test_random_networks_under_auto)
+    for variant in ('per_wave', 'row_lane', 'row_group') + (('auto',) if n <= 11 else ()):
         for method, kw in (('dopri45', {}), ('rk4', {'n_steps': 8192})):
             S, Y = m.calc_jacobian_batch(P, t[idx], return_states=True, variant=variant, method=method, **kw)
             assert m.last_info['status'].tolist() == [0, 0, 0, 0]
