@@ -1109,13 +1109,25 @@ extern "C" int sbm_project_trajectory_steps(sbm_project* p, int32_t V, int32_t* 
   return 0;
 }
 
-static int launch_assemble(const AssembleArgs& g, int V, hipStream_t s, const char* who) {
+static int lm_lds_limit(sbm_ctx* ctx);
+
+// The dynamic block of k_assemble and the kernel's static LDS (s_bad, padded to the dynamic block's alignment: 16 bytes,
+// read from the code object) have to fit the device's workgroup limit TOGETHER: compared alone with a literal 160 KB, a
+// dynamic block within 16 bytes of the limit was accepted here and refused by the runtime at the launch.
+static int launch_assemble(sbm_ctx* ctx, const AssembleArgs& g, int V, hipStream_t s, const char* who) {
   const int Gn = g.G > 0 ? g.G : 1;
   const int cw_ = g.q < 256 ? g.q : 256, rpp_ = 256 / cw_;
   const size_t lds = sizeof(double) * ((size_t)2 * g.R + 3 * Gn + 4 + (size_t)Gn * g.q + (size_t)2 * Gn * rpp_ * g.q) +
                      sizeof(double) * 2 * (size_t)g.R + sizeof(int) * (7 * (size_t)g.R + 2) +   // + the staged row tables
                      sizeof(double) * (size_t)g.NW;                                               // + custom-row weights
-  if (lds > 160 * 1024) return sbm_fail(SBM_E_ARG, "%s: project too large for the assembly kernel (%zu B of LDS)", who, lds);
+  static const size_t stat = [] {   // asked once: the kernel is the same on every device
+    hipFuncAttributes fa;
+    return hipFuncGetAttributes(&fa, (const void*)k_assemble) == hipSuccess ? (size_t)fa.sharedSizeBytes : (size_t)16;
+  }();
+  const size_t limit = (size_t)lm_lds_limit(ctx);
+  if (lds + stat > limit)
+    return sbm_fail(SBM_E_ARG, "%s: project too large for the assembly kernel (%zu B of LDS + %zu B static, the workgroup's limit is %zu B)",
+                    who, lds, stat, limit);
   if (lds > 64 * 1024) SBM_HIP(hipFuncSetAttribute((const void*)k_assemble, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(k_assemble, dim3(V), dim3(256), lds, s, g);
   SBM_HIP(hipGetLastError());
@@ -1210,7 +1222,7 @@ static int project_run(sbm_project* p, const double* Theta, int V, const sbm_int
   g.sims = sims ? sims : p->sims.p; g.Rout = Rout; g.sf = sf; g.norms = norms; g.status = status; g.n_steps = n_steps;
   g.J = sens ? J : nullptr; g.Jmodel = sens ? Jmodel : nullptr; g.grad = sens ? grad : nullptr;
   g.sf_grad = sens ? sf_grad : nullptr;
-  return launch_assemble(g, V, s, who);
+  return launch_assemble(m->ctx, g, V, s, who);
 }
 
 extern "C" int sbm_residuals_batch(sbm_project* p, const double* Theta, int32_t V, const sbm_integrator_opts* opts,
@@ -1284,7 +1296,7 @@ extern "C" int sbm_loss_eval_host(sbm_ctx* ctx, const sbm_loss_desc* d, int32_t 
     g.sims_in = b_sims.p; g.Jm_in = Jm ? b_Jm.p : nullptr;
     g.Rout = b_R.p; g.sf = b_sf.p; g.norms = b_norms.p; g.status = b_status.p;
     g.J = J ? b_J.p : nullptr; g.sf_grad = Jm ? b_sfg.p : nullptr;
-    rc = launch_assemble(g, V, s, who);
+    rc = launch_assemble(ctx, g, V, s, who);
   }
   hipError_t e = hipSuccess;
   if (!rc) {
