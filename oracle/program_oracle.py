@@ -1,5 +1,5 @@
 """ORACLE (test infrastructure, not product code): the stack machine that evaluates compiled 'custom' observables in
-the assembly kernel (csrc/sbm_core.hip::sbm_prog_eval, opcodes of include/sbm.h), restated in Python so that the
+the assembly kernel (csrc/sbm_observable_program.hpp::sbm_prog_eval, opcodes of include/sbm.h), restated in Python so that the
 compiler (sysbio_modeling_amd/project/observables.py) can be checked without a GPU.
 Only tests/ may import this."""
 import math

@@ -1,15 +1,15 @@
 // sbm_core.hip -- libsbm_hip.so: the C ABI of include/sbm.h.
 //
-// Contexts, plugin loading, batched simulate / sensitivity entry points, and the
-// model-independent Project kernels:
-//   k_gather_params   theta -> per-experiment parameter vectors
-//                     (Project.get_experiment_parameters, project/base_project.py:343-363)
-//   k_assemble        fused measurement sampling + 'direct'/'sum' mapping + linear scale
-//                     factors + weighted residuals + log-parameter chain rule + scaled
-//                     Jacobian (base_project.py:365-391,443-488; project/utils.py:10-89;
-//                     loss_functions/squared_loss/squared_loss_function.py:27-80;
-//                     linear_scale_factor.py:27-42)
-// and the host side -- argument checks, LDS sizes, launches (launch_lds) -- of the kernels kept in headers of their own:
+// Contexts, plugin loading, batched simulate / sensitivity entry points, and the host side -- argument checks, LDS
+// sizes, launches (launch_lds) -- of the kernels kept in headers of their own:
+//   sbm_assemble.hpp        k_gather_params, k_fill_grids, k_assemble: the model-independent Project kernels (theta ->
+//                           per-experiment parameter vectors; fused measurement sampling + mapping + scale factors +
+//                           weighted residuals + scaled Jacobian), with AssembleLds, the one layout of k_assemble's
+//                           dynamic LDS that the kernel carves and launch_assemble sizes
+//   sbm_observable_program.hpp  sbm_prog_eval, sbm_prog_check: interpreter and checker of the custom observables'
+//                           postfix programs (plain C++, no HIP)
+//   sbm_project_check.hpp   sbm_project_desc_check, sbm_loss_desc_check: everything sbm_project_load and
+//                           sbm_loss_eval_host verify of a descriptor before they touch the device (plain C++, no HIP)
 //   sbm_lm.hpp              k_lm_step, k_lm_trust[_held|_bounded], k_lm_update, k_lm_accept: the fitting loop (batched Levenberg-Marquardt
 //                           step, lmder's trust-region step and bookkeeping)
 //   sbm_sampler.hpp         k_sf_entropy, k_mh_propose, k_mh_accept, k_mh_accept_hastings: scale-factor entropy integrals
@@ -31,9 +31,11 @@
 #include <vector>
 
 #include "sbm_plugin.h"
+#include "sbm_assemble.hpp"
 #include "sbm_block_reduce.hpp"
 #include "sbm_ensemble_stats.hpp"
 #include "sbm_lm.hpp"
+#include "sbm_project_check.hpp"
 #include "sbm_sampler.hpp"
 #include "sbm_sampling_axes.hpp"
 
@@ -56,17 +58,25 @@ static int sbm_fail(int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return sbm_fail(-2, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
-enum { SBM_E_ARG = -1, SBM_E_HIP = -2, SBM_E_PLUGIN = -3 };
+enum { SBM_E_HIP = -2, SBM_E_PLUGIN = -3 };   // SBM_E_ARG = -1: sbm_observable_program.hpp, with the checks that return it
 
 // ---------------------------------------------------------------------------
 // objects
 // ---------------------------------------------------------------------------
 struct sbm_model;
 
+// A device array that grows on demand and is freed with its owner.  Whoever destroys one makes sure first that the
+// device is current and that nothing on the stream still uses it.
 template <class T>
 struct DevBuf {
   T* p = nullptr;
   size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
   int reserve(size_t want) {
     if (want <= n) return 0;
     if (p) (void)hipFree(p);
@@ -75,11 +85,6 @@ struct DevBuf {
     if (hipMalloc((void**)&p, want * sizeof(T)) != hipSuccess) return -1;
     n = want;
     return 0;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
   }
 };
 
@@ -153,9 +158,6 @@ extern "C" int sbm_ctx_create(int device, void* stream, sbm_ctx** out) {
 extern "C" int sbm_ctx_destroy(sbm_ctx* c) {
   if (!c) return 0;
   if (c->own_stream) (void)hipStreamDestroy(c->stream);
-  c->ens_flag.release();
-  c->ens_idx.release();
-  c->ens_n.release();
   delete c;
   return 0;
 }
@@ -202,7 +204,6 @@ extern "C" int sbm_model_unload(sbm_model* m) {
   if (!m) return 0;
   // the plugin's code object stays registered with the HIP runtime: do not dlclose
   (void)hipSetDevice(m->ctx->device);
-  m->order.release(); m->cost_steps.release(); m->cost_rej.release();
   delete m;
   return 0;
 }
@@ -451,408 +452,6 @@ extern "C" int sbm_sens_batch_host(sbm_model* m, const double* P, int32_t V, con
 // ===========================================================================
 // Project
 // ===========================================================================
-// trajectory id = v * E + e
-
-// theta -> P.  grid: ceil(V*E*NP / 256)
-__global__ void k_gather_params(const double* __restrict__ Theta, const int32_t* __restrict__ pmap,
-                                const double* __restrict__ pfixed, int V, int E, int NP, int q,
-                                double* __restrict__ P) {
-  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t total = (size_t)V * E * NP;
-  if (idx >= total) return;
-  const int m = (int)(idx % NP);
-  const size_t ve = idx / NP;
-  const int e = (int)(ve % E);
-  const size_t v = ve / E;
-  const int g = pmap[e * NP + m];
-  P[idx] = (g >= 0) ? exp(Theta[v * q + g]) : pfixed[e * NP + m];
-}
-
-// per-trajectory grid descriptors (same for every vector): grid = ceil(V*E/256)
-__global__ void k_fill_grids(const int32_t* __restrict__ tgrid_off, int V, int E, int32_t* __restrict__ goff,
-                             int32_t* __restrict__ glen) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= V * E) return;
-  const int e = idx % E;
-  goff[idx] = tgrid_off[e];
-  glen[idx] = tgrid_off[e + 1] - tgrid_off[e];
-}
-
-struct AssembleArgs {
-  // static project data
-  int E, q, R, G, NPR, NSP, NP, NV, NK, n_t, compat, loss;
-  const int32_t *row_exp, *row_tidx, *row_var_off, *row_vars, *row_sf, *prior_idx, *sfp_group;
-  const double *row_data, *row_sigma, *prior_mean, *prior_sigma, *sfp_mean, *sfp_sigma;
-  const int32_t *inv_ptr, *inv_m;  // [E][q+1] CSR: model params mapped to project column c in experiment e
-  const int32_t* sens_col;
-  // per call
-  const double* Theta;        // [V][q]
-  const double* Y;            // [V*E][n_t][NV]
-  const double* S;            // [V*E][n_t][NV][NK]   (nullable: residuals only)
-  const int32_t* traj_status; // [V*E]
-  const int32_t* traj_steps;  // [V*E]
-  double* sims;               // [V][R]       (scratch or user)
-  double* Rout;               // [V][R+NPR]
-  double* sf;                 // [V][G]       nullable
-  double* norms;              // [V]          nullable
-  int32_t* status;            // [V]          nullable
-  int32_t* n_steps;           // [V]          nullable: sum over the vector's trajectories
-  double* J;                  // [V][R+NPR][q] nullable
-  double* Jmodel;             // [V][R][q]     nullable
-  double* grad;               // [V][q]        nullable
-  double* sf_grad;            // [V][G][q]     nullable
-  // direct mode (sbm_loss_eval): caller-supplied simulations / model Jacobian instead of Y / S
-  const double* sims_in;      // [V][R]        nullable
-  const double* Jm_in;        // [V][R][q]     nullable
-  const int32_t* row_plain;   // [R] nullable: 1 = row keeps the plain (s - d)/sigma form under the log loss
-  // custom observables: row_prog[r] = program or -1; row_w0[r] = first slot of the row's dg/dy weights in the LDS
-  // table (or -1); prog_base[c] = first subprogram of program c in prog_sub_off
-  int NW;                     // total weight slots (sum of the variable counts of the custom rows)
-  const int32_t *row_prog, *row_w0, *prog_base, *prog_sub_off, *prog_code;
-  const double *prog_const, *row_time;
-};
-
-// One subprogram of a custom observable: a postfix stack machine (include/sbm.h, SBM_OP_*).  The host has
-// checked every program at load time (opcodes, operand ranges, stack depth <= SBM_PROG_MAX_STACK).
-__device__ double sbm_prog_eval(const int32_t* __restrict__ code, const double* __restrict__ consts,
-                                const double* __restrict__ Yb, const int32_t* __restrict__ vars, double t) {
-  double st[SBM_PROG_MAX_STACK];
-  int sp = 0;
-  for (int pc = 0;; ++pc) {
-    const int op = code[pc];
-    if (op == SBM_OP_END) break;
-    switch (op) {
-      case SBM_OP_VAR: st[sp++] = Yb[vars[code[++pc]]]; break;
-      case SBM_OP_CONST: st[sp++] = consts[code[++pc]]; break;
-      case SBM_OP_TIME: st[sp++] = t; break;
-      case SBM_OP_ADD: --sp; st[sp - 1] += st[sp]; break;
-      case SBM_OP_SUB: --sp; st[sp - 1] -= st[sp]; break;
-      case SBM_OP_MUL: --sp; st[sp - 1] *= st[sp]; break;
-      case SBM_OP_DIV: --sp; st[sp - 1] /= st[sp]; break;
-      case SBM_OP_POW: --sp; st[sp - 1] = pow(st[sp - 1], st[sp]); break;
-      case SBM_OP_POWI: {
-        int n = code[++pc];
-        const bool inv = n < 0;
-        n = inv ? -n : n;
-        double b = st[sp - 1], r = 1.0;
-        while (n) { if (n & 1) r *= b; b *= b; n >>= 1; }
-        st[sp - 1] = inv ? 1.0 / r : r;
-        break;
-      }
-      case SBM_OP_NEG: st[sp - 1] = -st[sp - 1]; break;
-      case SBM_OP_EXP: st[sp - 1] = exp(st[sp - 1]); break;
-      case SBM_OP_LOG: st[sp - 1] = log(st[sp - 1]); break;
-      case SBM_OP_SQRT: st[sp - 1] = sqrt(st[sp - 1]); break;
-      case SBM_OP_TANH: st[sp - 1] = tanh(st[sp - 1]); break;
-      case SBM_OP_SIN: st[sp - 1] = sin(st[sp - 1]); break;
-      case SBM_OP_COS: st[sp - 1] = cos(st[sp - 1]); break;
-      case SBM_OP_ABS: st[sp - 1] = fabs(st[sp - 1]); break;
-      case SBM_OP_SIGN: st[sp - 1] = st[sp - 1] > 0.0 ? 1.0 : (st[sp - 1] < 0.0 ? -1.0 : 0.0); break;
-      default: return __builtin_nan("");
-    }
-  }
-  return sp == 1 ? st[0] : __builtin_nan("");
-}
-
-// One block (256 threads) per parameter vector.
-// LDS: sims[R], B[G], sde[G], sds[G], dB[G][q] (Jacobian mode), reduction scratch.
-__global__ void __launch_bounds__(256) k_assemble(AssembleArgs a) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int v = blockIdx.x;
-  const int tid = threadIdx.x;
-  const int R = a.R, G = a.G, q = a.q, E = a.E;
-  double* s_sim = smem;                 // [R]
-  double* s_res = s_sim + R;            // [R]   weighted residuals
-  double* s_B = s_res + R;              // [max(G,1)]
-  double* s_sde = s_B + (G > 0 ? G : 1);
-  double* s_sds = s_sde + (G > 0 ? G : 1);
-  double* s_red = s_sds + (G > 0 ? G : 1);  // [4]
-  // row tables staged once per block: every thread of pass A / B would otherwise chase them through
-  // global memory for each of its elements (a chain of dependent loads per element: the kernel was bound
-  // by that latency, not by HBM)
-  double* s_d = s_red + 4;                  // [R] measurement
-  double* s_sg = s_d + R;                   // [R] sigma
-  int* s_roff = (int*)(s_sg + R);           // [R] (e * n_t + tidx) * NV: offset of the row's time point in the vector's Y block
-  int* s_rexp = s_roff + R;                 // [R] experiment
-  int* s_rv0 = s_rexp + R;                  // [R] first entry of the row's variable list
-  int* s_rnv = s_rv0 + R;                   // [R] its length
-  int* s_rvar = s_rnv + R;                  // [R] first variable (the only one of a 'direct' mapping)
-  int* s_rsf = s_rvar + R;                  // [R] scale-factor group or -1
-  int* s_rw0 = s_rsf + R;                   // [R + (R & 1)] first dg/dy weight slot of a custom row, -1 for plain rows
-  double* s_w = (double*)(s_rw0 + R + (R & 1));   // [NW] dg/dy_k of the custom rows at this vector's sampled states
-  double* s_dB = s_w + a.NW;                // 8-byte aligned.  [G][q], then the partial sums [2][G][rpp][q]
-  __shared__ int s_bad;
-
-  if (tid == 0) s_bad = 0;
-  for (int r = tid; r < R; r += blockDim.x) {
-    s_d[r] = a.row_data[r];
-    s_sg[r] = a.row_sigma[r];
-    s_rsf[r] = a.row_sf[r];
-    s_rw0[r] = (a.row_w0 && !a.sims_in) ? a.row_w0[r] : -1;
-    if (!a.sims_in) {
-      const int e = a.row_exp[r], v0 = a.row_var_off[r];
-      s_rexp[r] = e;
-      s_roff[r] = (e * a.n_t + a.row_tidx[r]) * a.NV;
-      s_rv0[r] = v0;
-      s_rnv[r] = a.row_var_off[r + 1] - v0;
-      s_rvar[r] = a.row_var_off[r + 1] > v0 ? a.row_vars[v0] : 0;
-    } else {
-      s_rexp[r] = 0; s_roff[r] = 0; s_rv0[r] = 0; s_rnv[r] = 0; s_rvar[r] = 0;
-    }
-  }
-  __syncthreads();
-  // status of the vector = worst status of its trajectories
-  int st = 0, steps = 0;
-  for (int e = tid; a.traj_status && e < E; e += blockDim.x) {
-    st = max(st, a.traj_status[(size_t)v * E + e]);
-    steps += a.traj_steps ? a.traj_steps[(size_t)v * E + e] : 0;
-  }
-  if (st != 0) atomicMax(&s_bad, st);
-  if (a.n_steps) {
-    const double tot = block_sum((double)steps, s_red);
-    if (tid == 0) a.n_steps[v] = (int32_t)tot;
-  }
-
-  // ---- 1. sample + map: sims[r] = sum_{var in vars(r)} Y[traj][tidx][var] ----
-  for (int r = tid; r < R; r += blockDim.x) {
-    double s = 0.0;
-    if (a.sims_in) {
-      s = a.sims_in[(size_t)v * R + r];
-    } else {
-      const double* Yb = a.Y + (size_t)v * E * a.n_t * a.NV + s_roff[r];
-      if (s_rw0[r] >= 0) {
-        // custom observable: value g(y), and dg/dy_k parked in LDS for the Jacobian pass
-        const int32_t* sub = a.prog_sub_off + a.prog_base[a.row_prog[r]];
-        const int32_t* vars = a.row_vars + s_rv0[r];
-        const double tr = a.row_time[r];
-        s = sbm_prog_eval(a.prog_code + sub[0], a.prog_const, Yb, vars, tr);
-        if (a.S)
-          for (int k = 0; k < s_rnv[r]; ++k)
-            s_w[s_rw0[r] + k] = sbm_prog_eval(a.prog_code + sub[1 + k], a.prog_const, Yb, vars, tr);
-      } else if (s_rnv[r] == 1) s = Yb[s_rvar[r]];
-      else for (int k = s_rv0[r]; k < s_rv0[r] + s_rnv[r]; ++k) s += Yb[a.row_vars[k]];
-    }
-    s_sim[r] = s;
-    // NaN simulations -> inf rows; the log loss cannot take a non-positive simulation either
-    const bool logrow = a.loss == SBM_LOSS_LOG_SQUARE && !(a.row_plain && a.row_plain[r]);
-    if (!(s == s) || (logrow && !(s > 0.0))) atomicMax(&s_bad, (int)SBM_NON_FINITE);
-  }
-  __syncthreads();
-  const int bad = s_bad;
-  if (a.status && tid == 0) a.status[v] = bad;
-
-  const int RT = R + a.NPR + a.NSP;
-  if (bad) {
-    // reference: NaN in simulations -> every residual / Jacobian entry is inf
-    // (squared_loss_function.py:28-32,46-50)
-    const double inf = __builtin_inf();
-    for (int r = tid; r < RT; r += blockDim.x) a.Rout[(size_t)v * RT + r] = inf;
-    if (a.sims) for (int r = tid; r < R; r += blockDim.x) a.sims[(size_t)v * R + r] = s_sim[r];
-    if (a.sf) for (int g = tid; g < G; g += blockDim.x) a.sf[(size_t)v * G + g] = __builtin_nan("");
-    if (a.norms && tid == 0) a.norms[v] = inf;
-    if (a.J) for (size_t i = tid; i < (size_t)RT * q; i += blockDim.x) a.J[(size_t)v * RT * q + i] = inf;
-    if (a.Jmodel) for (size_t i = tid; i < (size_t)R * q; i += blockDim.x) a.Jmodel[(size_t)v * R * q + i] = inf;
-    if (a.grad) for (int c = tid; c < q; c += blockDim.x) a.grad[(size_t)v * q + c] = inf;
-    if (a.sf_grad) for (int i = tid; i < G * q; i += blockDim.x) a.sf_grad[(size_t)v * G * q + i] = __builtin_nan("");
-    return;
-  }
-  if (a.sims) for (int r = tid; r < R; r += blockDim.x) a.sims[(size_t)v * R + r] = s_sim[r];
-
-  // ---- 2. scale factors B_g = sum(s d / sigma^2) / sum(s^2 / sigma^2) ----
-  for (int g = 0; g < G; ++g) {
-    double sde = 0.0, sds = 0.0;
-    for (int r = tid; r < R; r += blockDim.x) {
-      if (s_rsf[r] == g) {
-        if (a.loss == SBM_LOSS_LOG_SQUARE) {
-          // log_scale_factor.py:17-28: weights 1/(sigma/d)^2; log B = sum(w (log d - log s)) / sum(w)
-          const double w = (s_d[r] * s_d[r]) / (s_sg[r] * s_sg[r]);
-          sde += (log(s_d[r]) - log(s_sim[r])) * w;
-          sds += w;
-        } else {
-          const double w = 1.0 / (s_sg[r] * s_sg[r]);
-          sde += s_sim[r] * s_d[r] * w;
-          sds += s_sim[r] * s_sim[r] * w;
-        }
-      }
-    }
-    sde = block_sum(sde, s_red);
-    sds = block_sum(sds, s_red);
-    if (tid == 0) {
-      s_sde[g] = sde;
-      s_sds[g] = sds;
-      const double B = (a.loss == SBM_LOSS_LOG_SQUARE) ? exp(sde / sds) : sde / sds;
-      s_B[g] = B;
-      if (a.sf) a.sf[(size_t)v * G + g] = B;
-    }
-  }
-  __syncthreads();
-
-  // ---- 3. residuals ----
-  double nrm = 0.0;
-  for (int r = tid; r < RT; r += blockDim.x) {
-    double res;
-    if (r < R) {
-      const int g = s_rsf[r];
-      const double B = g >= 0 ? s_B[g] : 1.0;
-      const bool logrow = a.loss == SBM_LOSS_LOG_SQUARE && !(a.row_plain && a.row_plain[r]);
-      res = logrow ? (log(B * s_sim[r]) - log(s_d[r])) / s_sg[r]
-                   : (B * s_sim[r] - s_d[r]) / s_sg[r];
-      s_res[r] = res;
-    } else if (r < R + a.NPR) {
-      const int k = r - R;
-      res = (a.Theta[(size_t)v * q + a.prior_idx[k]] - a.prior_mean[k]) / a.prior_sigma[k];
-    } else {
-      const int k = r - R - a.NPR;  // (log B - prior)/sigma, linear_scale_factor.py:55-61
-      res = (log(s_B[a.sfp_group[k]]) - a.sfp_mean[k]) / a.sfp_sigma[k];
-    }
-    a.Rout[(size_t)v * RT + r] = res;
-    nrm += res * res;
-  }
-  nrm = block_sum(nrm, s_red);
-  if (a.norms && tid == 0) a.norms[v] = nrm;
-  if (!a.J && !a.Jmodel && !a.grad && !a.sf_grad) return;
-
-  // ---- 4. model Jacobian with the log-parameter chain rule (base_project.py:450-455,482-485):
-  //      Jm[r][c] = exp(theta_c) * sum_{model params m of experiment e reading slot c} sum_{var in vars(r)} S[var][m]
-  // pass A: write Jm, accumulate per SF group the two products J^T (d/sigma^2), J^T (s/sigma^2)
-  double* Jv = a.J ? a.J + (size_t)v * RT * q : nullptr;
-  double* Jm = a.Jmodel ? a.Jmodel + (size_t)v * R * q : nullptr;
-  const double* th = a.Theta + (size_t)v * q;
-  // partial sums owned by ONE thread each, [which][g][row lane][c]: no atomics, and the final
-  // reduction runs in a fixed order, so results are bitwise reproducible run to run
-  const int nthr = blockDim.x;
-  const int cw = q < nthr ? q : nthr;  // columns handled side by side (consecutive threads -> consecutive columns)
-  const int rpp = nthr / cw;           // row lanes
-  const int Gn = G > 0 ? G : 1;
-  double* s_part = s_dB + (size_t)Gn * q;  // [2][Gn][rpp][q]
-  for (int i = tid; i < 2 * Gn * rpp * q; i += nthr) s_part[i] = 0.0;
-  __syncthreads();
-
-  const int cl = tid % cw, rl = tid / cw;
-  for (int c0 = 0; c0 < q; c0 += cw) {
-    const int c = c0 + cl;
-    if (c >= q || rl >= rpp) continue;
-    const double dth = a.Jm_in ? 1.0 : exp(th[c]);
-    int gcur = -1;
-    int e_cur = -1, k0 = 0, k1 = 0, sc1 = -1;
-    double jde = 0.0, jds = 0.0;
-    for (int r = rl; r < R; r += rpp) {
-      double jm = 0.0;
-      if (a.Jm_in) {
-        jm = a.Jm_in[((size_t)v * R + r) * q + c];
-      } else {
-        const int e = s_rexp[r];
-        if (e != e_cur) {   // rows are sorted by experiment: the column's model parameters change rarely
-          e_cur = e;
-          k0 = a.inv_ptr[e * (q + 1) + c];
-          k1 = a.inv_ptr[e * (q + 1) + c + 1];
-          sc1 = (k1 - k0 == 1) ? a.sens_col[a.inv_m[k0]] : -2;   // the common case: one model parameter per slot
-        }
-        const double* Sb = a.S + ((size_t)v * E * a.n_t * a.NV + s_roff[r]) * a.NK;
-        const int w0 = s_rw0[r];
-        if (sc1 >= 0 && s_rnv[r] == 1 && w0 < 0) {
-          jm = Sb[(size_t)s_rvar[r] * a.NK + sc1];
-        } else if (sc1 != -1) {
-          for (int k = k0; k < k1; ++k) {
-            const int sc = a.sens_col[a.inv_m[k]];
-            if (sc < 0) continue;
-            if (w0 < 0) {
-              for (int kk = s_rv0[r]; kk < s_rv0[r] + s_rnv[r]; ++kk) jm += Sb[(size_t)a.row_vars[kk] * a.NK + sc];
-            } else {   // custom observable: sum_k dg/dy_k * S[var_k][sc]
-              for (int kk = 0; kk < s_rnv[r]; ++kk)
-                jm = fma(s_w[w0 + kk], Sb[(size_t)a.row_vars[s_rv0[r] + kk] * a.NK + sc], jm);
-            }
-          }
-        }
-        jm *= dth;
-      }
-      if (Jm) Jm[(size_t)r * q + c] = jm;
-      if (Jv) Jv[(size_t)r * q + c] = jm;
-      const int g = s_rsf[r];
-      if (g != gcur) {  // rows of one group are mostly consecutive: flush on change
-        if (gcur >= 0) {
-          s_part[((size_t)(0 * Gn + gcur) * rpp + rl) * q + c] += jde;
-          s_part[((size_t)(1 * Gn + gcur) * rpp + rl) * q + c] += jds;
-        }
-        gcur = g; jde = 0.0; jds = 0.0;
-      }
-      if (g >= 0) {
-        if (a.loss == SBM_LOSS_LOG_SQUARE) {  // log_scale_factor.py:30-36: sum J / (s (sigma/d)^2)
-          jde += jm * (s_d[r] * s_d[r]) / (s_sg[r] * s_sg[r] * s_sim[r]);
-        } else {
-          const double w = 1.0 / (s_sg[r] * s_sg[r]);
-          jde += jm * s_d[r] * w;
-          jds += jm * s_sim[r] * w;
-        }
-      }
-    }
-    if (gcur >= 0) {
-      s_part[((size_t)(0 * Gn + gcur) * rpp + rl) * q + c] += jde;
-      s_part[((size_t)(1 * Gn + gcur) * rpp + rl) * q + c] += jds;
-    }
-  }
-  __syncthreads();
-  // dB_g/dtheta_c = jde/sds - 2 sde jds / sds^2   (linear_scale_factor.py:33-42)
-  for (int i = tid; i < G * q; i += nthr) {
-    const int g = i / q, c = i - g * q;
-    double jde = 0.0, jds = 0.0;
-    for (int l = 0; l < rpp; ++l) {
-      jde += s_part[((size_t)(0 * Gn + g) * rpp + l) * q + c];
-      jds += s_part[((size_t)(1 * Gn + g) * rpp + l) * q + c];
-    }
-    const double sds = s_sds[g], sde = s_sde[g];
-    // square: dB = jde/sds - 2 sde jds/sds^2 ; log: dB = B * (-1/W) sum J/(s sigma'^2)
-    const double db = (a.loss == SBM_LOSS_LOG_SQUARE) ? -s_B[g] * jde / sds
-                                                      : jde / sds - 2.0 * sde * jds / (sds * sds);
-    s_dB[i] = db;
-    if (a.sf_grad) a.sf_grad[(size_t)v * G * q + i] = db;
-  }
-  __syncthreads();
-
-  // pass B: J = B*Jm + sim (x) dB ; reference_compat: not divided by sigma, prior rows zero
-  if (Jv) {
-    for (size_t i = tid; i < (size_t)RT * q; i += blockDim.x) {
-      const int r = (int)(i / q), c = (int)(i - (size_t)r * q);
-      double val;
-      if (r < R) {
-        const int g = s_rsf[r];
-        val = Jv[i];
-        if (a.loss == SBM_LOSS_LOG_SQUARE && !(a.row_plain && a.row_plain[r])) {
-          // log_squared_loss_function.py:66-98: J/s (+ (dB/dtheta)/B for rows with a scale factor)
-          val = val / s_sim[r];
-          if (g >= 0) val += s_dB[g * q + c] / s_B[g];
-        } else if (g >= 0) {
-          val = s_B[g] * val + s_sim[r] * s_dB[g * q + c];
-        }
-        if (!a.compat) val /= s_sg[r];
-      } else if (r < R + a.NPR) {
-        const int k = r - R;
-        val = (!a.compat && a.prior_idx[k] == c) ? 1.0 / a.prior_sigma[k] : 0.0;
-      } else {
-        const int k = r - R - a.NPR;  // (dB/dtheta)/B, linear_scale_factor.py:44-53
-        const int g = a.sfp_group[k];
-        val = s_dB[g * q + c] / s_B[g];
-        if (!a.compat) val /= a.sfp_sigma[k];
-      }
-      Jv[i] = val;
-    }
-  }
-  // gradient of 0.5*sum r^2: (J^T r) with the Jacobian as returned (reference :803-805)
-  if (a.grad) {
-    __syncthreads();
-    for (int c = tid; c < q; c += blockDim.x) {
-      double gsum = 0.0;
-      if (Jv) {
-        for (int r = 0; r < RT; ++r) {
-          const double res = a.Rout[(size_t)v * RT + r];
-          gsum += Jv[(size_t)r * q + c] * res;
-        }
-      }
-      a.grad[(size_t)v * q + c] = gsum;
-    }
-  }
-}
-
 template <class T>
 static int upload(DevBuf<T>& b, const T* h, size_t n, hipStream_t s) {
   if (n == 0) n = 1;  // keep pointers non-NULL
@@ -863,111 +462,11 @@ static int upload(DevBuf<T>& b, const T* h, size_t n, hipStream_t s) {
 
 extern "C" int sbm_project_load(sbm_model* m, const sbm_project_desc* d, sbm_project** out) {
   if (!m || !d || !out) return sbm_fail(SBM_E_ARG, "sbm_project_load: NULL argument");
+  // validated on the host: the kernels index with these arrays and run the custom-observable programs unchecked
+  sbm_project_tables t;
+  if (int rc = sbm_project_desc_check(d, m->info.n_vars, m->info.n_params, m->info.n_sens, g_err, sizeof(g_err), &t)) return rc;
   const int E = d->n_experiments, q = d->n_project_params, R = d->n_rows, G = d->n_sf_groups,
-            NPR = d->n_prior_rows, NSP = d->n_sf_prior_rows, NP = m->info.n_params;
-  if (d->loss_type != SBM_LOSS_SQUARE && d->loss_type != SBM_LOSS_LOG_SQUARE)
-    return sbm_fail(SBM_E_ARG, "sbm_project_load: unknown loss_type %d", d->loss_type);
-  if (E <= 0 || q <= 0 || R < 0 || G < 0 || NPR < 0 || NSP < 0)
-    return sbm_fail(SBM_E_ARG, "sbm_project_load: bad sizes E=%d q=%d R=%d G=%d", E, q, R, G);
-  if (!d->pmap || !d->pfixed || !d->sens_col || !d->tgrid_off || !d->tgrid || (R && (!d->row_exp || !d->row_tidx ||
-      !d->row_var_off || !d->row_vars || !d->row_data || !d->row_sigma || !d->row_sf)))
-    return sbm_fail(SBM_E_ARG, "sbm_project_load: NULL array in descriptor");
-  // validate on the host: the kernels index with these
-  int n_t_max = 0;
-  for (int e = 0; e < E; ++e) {
-    const int len = d->tgrid_off[e + 1] - d->tgrid_off[e];
-    if (len <= 0) return sbm_fail(SBM_E_ARG, "sbm_project_load: experiment %d has no output times", e);
-    for (int k = d->tgrid_off[e] + 1; k < d->tgrid_off[e + 1]; ++k)
-      if (!(d->tgrid[k] >= d->tgrid[k - 1])) return sbm_fail(SBM_E_ARG, "sbm_project_load: tgrid of experiment %d not sorted", e);
-    if (d->tgrid[d->tgrid_off[e]] < 0.0) return sbm_fail(SBM_E_ARG, "sbm_project_load: negative output time");
-    n_t_max = len > n_t_max ? len : n_t_max;
-    for (int k = 0; k < NP; ++k) {
-      const int g = d->pmap[e * NP + k];
-      if (g >= q) return sbm_fail(SBM_E_ARG, "sbm_project_load: pmap[%d][%d]=%d >= q=%d", e, k, g, q);
-    }
-  }
-  for (int k = 0; k < NP; ++k)
-    if (d->sens_col[k] >= m->info.n_sens) return sbm_fail(SBM_E_ARG, "sbm_project_load: sens_col out of range");
-  for (int r = 0; r < R; ++r) {
-    const int e = d->row_exp[r];
-    if (e < 0 || e >= E) return sbm_fail(SBM_E_ARG, "sbm_project_load: row %d experiment %d", r, e);
-    const int len = d->tgrid_off[e + 1] - d->tgrid_off[e];
-    if (d->row_tidx[r] < 0 || d->row_tidx[r] >= len) return sbm_fail(SBM_E_ARG, "sbm_project_load: row %d time index", r);
-    if (d->row_var_off[r + 1] < d->row_var_off[r]) return sbm_fail(SBM_E_ARG, "sbm_project_load: row_var_off");
-    for (int k = d->row_var_off[r]; k < d->row_var_off[r + 1]; ++k)
-      if (d->row_vars[k] < 0 || d->row_vars[k] >= m->info.n_vars)
-        return sbm_fail(SBM_E_ARG, "sbm_project_load: row %d maps to variable %d of %d", r, d->row_vars[k], m->info.n_vars);
-    if (d->row_sf[r] >= G) return sbm_fail(SBM_E_ARG, "sbm_project_load: row %d sf group %d", r, d->row_sf[r]);
-    if (d->row_sigma[r] == 0.0) return sbm_fail(SBM_E_ARG, "sbm_project_load: row %d has sigma 0", r);
-    if (d->loss_type == SBM_LOSS_LOG_SQUARE && !(d->row_data[r] > 0.0))
-      return sbm_fail(SBM_E_ARG, "sbm_project_load: LogSquare loss cannot handle measurements smaller or equal to zero (row %d)", r);
-  }
-  // custom observables: every program is checked here, once, so that the interpreter in the kernel can run unchecked
-  const int NPG = d->n_programs;
-  std::vector<int32_t> prog_base((size_t)(NPG > 0 ? NPG : 0) + 1, 0), row_w0((size_t)(R > 0 ? R : 1), -1);
-  int n_weights = 0;
-  if (NPG < 0) return sbm_fail(SBM_E_ARG, "sbm_project_load: n_programs < 0");
-  if (NPG > 0) {
-    if (!d->row_prog || !d->prog_nvars || !d->prog_sub_off || !d->prog_code || !d->row_time || d->n_prog_code <= 0 ||
-        (d->n_prog_const > 0 && !d->prog_const))
-      return sbm_fail(SBM_E_ARG, "sbm_project_load: NULL program table");
-    for (int c = 0; c < NPG; ++c) {
-      if (d->prog_nvars[c] < 0 || d->prog_nvars[c] > 64) return sbm_fail(SBM_E_ARG, "sbm_project_load: program %d lists %d variables", c, d->prog_nvars[c]);
-      prog_base[c + 1] = prog_base[c] + 1 + d->prog_nvars[c];
-    }
-    for (int c = 0; c < NPG; ++c) {
-      for (int sidx = prog_base[c]; sidx < prog_base[c + 1]; ++sidx) {
-        int pc = d->prog_sub_off[sidx], depth = 0;
-        const int end = d->prog_sub_off[sidx + 1];
-        if (pc < 0 || end > d->n_prog_code || pc >= end) return sbm_fail(SBM_E_ARG, "sbm_project_load: program %d: bad subprogram bounds", c);
-        bool closed = false;
-        for (; pc < end && !closed; ++pc) {
-          const int op = d->prog_code[pc];
-          switch (op) {
-            case SBM_OP_END: closed = true; break;
-            case SBM_OP_VAR:
-              if (++pc >= end || d->prog_code[pc] < 0 || d->prog_code[pc] >= d->prog_nvars[c])
-                return sbm_fail(SBM_E_ARG, "sbm_project_load: program %d: variable operand out of range", c);
-              ++depth; break;
-            case SBM_OP_CONST:
-              if (++pc >= end || d->prog_code[pc] < 0 || d->prog_code[pc] >= d->n_prog_const)
-                return sbm_fail(SBM_E_ARG, "sbm_project_load: program %d: constant operand out of range", c);
-              ++depth; break;
-            case SBM_OP_TIME: ++depth; break;
-            case SBM_OP_ADD: case SBM_OP_SUB: case SBM_OP_MUL: case SBM_OP_DIV: case SBM_OP_POW:
-              if (depth < 2) return sbm_fail(SBM_E_ARG, "sbm_project_load: program %d: stack underflow", c);
-              --depth; break;
-            case SBM_OP_POWI:
-              if (++pc >= end || d->prog_code[pc] < -64 || d->prog_code[pc] > 64)
-                return sbm_fail(SBM_E_ARG, "sbm_project_load: program %d: integer power out of range", c);
-              if (depth < 1) return sbm_fail(SBM_E_ARG, "sbm_project_load: program %d: stack underflow", c);
-              break;
-            case SBM_OP_NEG: case SBM_OP_EXP: case SBM_OP_LOG: case SBM_OP_SQRT: case SBM_OP_TANH: case SBM_OP_SIN:
-            case SBM_OP_COS: case SBM_OP_ABS: case SBM_OP_SIGN:
-              if (depth < 1) return sbm_fail(SBM_E_ARG, "sbm_project_load: program %d: stack underflow", c);
-              break;
-            default: return sbm_fail(SBM_E_ARG, "sbm_project_load: program %d: unknown opcode %d", c, op);
-          }
-          if (depth > SBM_PROG_MAX_STACK) return sbm_fail(SBM_E_ARG, "sbm_project_load: program %d needs a stack deeper than %d", c, SBM_PROG_MAX_STACK);
-        }
-        if (!closed || depth != 1) return sbm_fail(SBM_E_ARG, "sbm_project_load: program %d: subprogram does not leave exactly one value", c);
-      }
-    }
-    for (int r = 0; r < R; ++r) {
-      const int c = d->row_prog[r];
-      if (c >= NPG) return sbm_fail(SBM_E_ARG, "sbm_project_load: row %d program %d of %d", r, c, NPG);
-      if (c < 0) continue;
-      if (d->row_var_off[r + 1] - d->row_var_off[r] != d->prog_nvars[c])
-        return sbm_fail(SBM_E_ARG, "sbm_project_load: row %d lists %d variables, its program %d takes %d", r,
-                        d->row_var_off[r + 1] - d->row_var_off[r], c, d->prog_nvars[c]);
-      row_w0[r] = n_weights;
-      n_weights += d->prog_nvars[c];
-    }
-  }
-  for (int k = 0; k < NPR; ++k)
-    if (d->prior_idx[k] < 0 || d->prior_idx[k] >= q) return sbm_fail(SBM_E_ARG, "sbm_project_load: prior index");
-  for (int k = 0; k < NSP; ++k)
-    if (d->sf_prior_group[k] < 0 || d->sf_prior_group[k] >= G) return sbm_fail(SBM_E_ARG, "sbm_project_load: sf prior group");
+            NPR = d->n_prior_rows, NSP = d->n_sf_prior_rows, NP = m->info.n_params, NPG = d->n_programs;
 
   SBM_HIP(hipSetDevice(m->ctx->device));
   hipStream_t s = m->ctx->stream;
@@ -975,7 +474,7 @@ extern "C" int sbm_project_load(sbm_model* m, const sbm_project_desc* d, sbm_pro
   p->model = m;
   p->E = E; p->q = q; p->R = R; p->G = G; p->NPR = NPR; p->NSP = NSP; p->compat = d->reference_compat;
   p->loss = d->loss_type;
-  p->n_params = NP; p->n_vars = m->info.n_vars; p->n_sens = m->info.n_sens; p->n_t_max = n_t_max;
+  p->n_params = NP; p->n_vars = m->info.n_vars; p->n_sens = m->info.n_sens; p->n_t_max = t.n_t_max;
 
   // inverse map: for experiment e and project column c, the model params that read it
   std::vector<int32_t> inv_ptr((size_t)E * (q + 1), 0), inv_m;
@@ -1022,12 +521,12 @@ extern "C" int sbm_project_load(sbm_model* m, const sbm_project_desc* d, sbm_pro
   bad |= upload(p->inv_ptr, inv_ptr.data(), inv_ptr.size(), s);
   bad |= upload(p->inv_m, inv_m.data(), inv_m.size(), s);
   p->n_programs = NPG;
-  p->n_custom_weights = n_weights;
+  p->n_custom_weights = t.n_weights;
   if (NPG > 0) {
     bad |= upload(p->row_prog, d->row_prog, (size_t)R, s);
-    bad |= upload(p->row_w0, row_w0.data(), (size_t)R, s);
-    bad |= upload(p->prog_base, prog_base.data(), prog_base.size(), s);
-    bad |= upload(p->prog_sub_off, d->prog_sub_off, (size_t)prog_base[NPG] + 1, s);
+    bad |= upload(p->row_w0, t.row_w0.data(), (size_t)R, s);
+    bad |= upload(p->prog_base, t.prog_base.data(), t.prog_base.size(), s);
+    bad |= upload(p->prog_sub_off, d->prog_sub_off, (size_t)t.prog_base[NPG] + 1, s);
     bad |= upload(p->prog_code, d->prog_code, (size_t)d->n_prog_code, s);
     bad |= upload(p->prog_const, d->prog_const, (size_t)d->n_prog_const, s);
     bad |= upload(p->row_time, d->row_time, (size_t)R, s);
@@ -1044,17 +543,6 @@ extern "C" int sbm_project_load(sbm_model* m, const sbm_project_desc* d, sbm_pro
 extern "C" int sbm_project_unload(sbm_project* p) {
   if (!p) return 0;
   (void)hipSetDevice(p->model->ctx->device);
-  p->pmap.release(); p->sens_col.release(); p->tgrid_off.release(); p->grid_len.release(); p->row_exp.release();
-  p->row_tidx.release(); p->row_var_off.release(); p->row_vars.release(); p->row_sf.release(); p->prior_idx.release();
-  p->inv_ptr.release(); p->inv_m.release(); p->pfixed.release(); p->tgrid.release(); p->row_data.release();
-  p->row_sigma.release(); p->prior_mean.release(); p->prior_sigma.release();
-  p->sfp_group.release(); p->sfp_mean.release(); p->sfp_sigma.release(); p->sfg_mean.release(); p->sfg_sigma.release();
-  p->row_prog.release(); p->row_w0.release(); p->prog_base.release(); p->prog_sub_off.release(); p->prog_code.release();
-  p->prog_const.release(); p->row_time.release();
-  p->P.release(); p->Y.release(); p->S.release(); p->sims.release(); p->sf.release();
-  p->traj_status.release(); p->traj_steps.release(); p->traj_rej.release(); p->goff.release(); p->glen.release();
-  for (int l = 0; l < 2; ++l) { p->Yx[l].release(); p->Sx[l].release(); }
-  p->statx.release(); p->stepsx.release();
   delete p;
   return 0;
 }
@@ -1109,17 +597,30 @@ extern "C" int sbm_project_trajectory_steps(sbm_project* p, int32_t V, int32_t* 
   return 0;
 }
 
-static int lm_lds_limit(sbm_ctx* ctx);
+// ---------------------------------------------------------------------------------------------
+// Kernels with dynamic LDS: what a workgroup may have, and the launch.
+// ---------------------------------------------------------------------------------------------
+static int lm_lds_limit(sbm_ctx* ctx) {
+  int lim = 0;
+  if (hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess || lim <= 0) lim = 64 * 1024;
+  return lim;
+}
 
-// The dynamic block of k_assemble and the kernel's static LDS (s_bad, padded to the dynamic block's alignment: 16 bytes,
-// read from the code object) have to fit the device's workgroup limit TOGETHER: compared alone with a literal 160 KB, a
-// dynamic block within 16 bytes of the limit was accepted here and refused by the runtime at the launch.
-static int launch_assemble(sbm_ctx* ctx, const AssembleArgs& g, int V, hipStream_t s, const char* who) {
-  const int Gn = g.G > 0 ? g.G : 1;
-  const int cw_ = g.q < 256 ? g.q : 256, rpp_ = 256 / cw_;
-  const size_t lds = sizeof(double) * ((size_t)2 * g.R + 3 * Gn + 4 + (size_t)Gn * g.q + (size_t)2 * Gn * rpp_ * g.q) +
-                     sizeof(double) * 2 * (size_t)g.R + sizeof(int) * (7 * (size_t)g.R + 2) +   // + the staged row tables
-                     sizeof(double) * (size_t)g.NW;                                               // + custom-row weights
+// `kernel` on the context's device and stream with `lds` bytes of dynamic LDS; more than 64 KB have to be asked for
+template <class... P, class... A>
+static int launch_lds(sbm_ctx* ctx, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, const A&... args) {
+  SBM_HIP(hipSetDevice(ctx->device));
+  if (lds > 64 * 1024) SBM_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, args...);
+  SBM_HIP(hipGetLastError());
+  return 0;
+}
+
+// The dynamic block of k_assemble (AssembleLds) and the kernel's static LDS (s_bad, padded to the dynamic block's
+// alignment: 16 bytes, read from the code object) have to fit the device's workgroup limit TOGETHER: compared alone with
+// a literal 160 KB, a dynamic block within 16 bytes of the limit was accepted here and refused by the runtime at the launch.
+static int launch_assemble(sbm_ctx* ctx, const AssembleArgs& g, int V, const char* who) {
+  const size_t lds = AssembleLds(g.R, g.G, g.q, g.NW, 256).bytes();
   static const size_t stat = [] {   // asked once: the kernel is the same on every device
     hipFuncAttributes fa;
     return hipFuncGetAttributes(&fa, (const void*)k_assemble) == hipSuccess ? (size_t)fa.sharedSizeBytes : (size_t)16;
@@ -1128,10 +629,28 @@ static int launch_assemble(sbm_ctx* ctx, const AssembleArgs& g, int V, hipStream
   if (lds + stat > limit)
     return sbm_fail(SBM_E_ARG, "%s: project too large for the assembly kernel (%zu B of LDS + %zu B static, the workgroup's limit is %zu B)",
                     who, lds, stat, limit);
-  if (lds > 64 * 1024) SBM_HIP(hipFuncSetAttribute((const void*)k_assemble, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_assemble, dim3(V), dim3(256), lds, s, g);
-  SBM_HIP(hipGetLastError());
-  return 0;
+  return launch_lds(ctx, k_assemble, dim3(V), dim3(256), lds, g);
+}
+
+// the static part of the kernel's arguments: the project's tables
+static AssembleArgs assemble_args(const sbm_project* p) {
+  AssembleArgs g;
+  memset(&g, 0, sizeof(g));
+  g.E = p->E; g.q = p->q; g.R = p->R; g.G = p->G; g.NPR = p->NPR; g.NSP = p->NSP;
+  g.NP = p->n_params; g.NV = p->n_vars; g.NK = p->n_sens; g.n_t = p->n_t_max;
+  g.compat = p->compat;
+  g.loss = p->loss;
+  g.row_exp = p->row_exp.p; g.row_tidx = p->row_tidx.p; g.row_var_off = p->row_var_off.p; g.row_vars = p->row_vars.p;
+  g.row_sf = p->row_sf.p; g.prior_idx = p->prior_idx.p; g.row_data = p->row_data.p; g.row_sigma = p->row_sigma.p;
+  g.prior_mean = p->prior_mean.p; g.prior_sigma = p->prior_sigma.p;
+  g.sfp_group = p->sfp_group.p; g.sfp_mean = p->sfp_mean.p; g.sfp_sigma = p->sfp_sigma.p; g.inv_ptr = p->inv_ptr.p; g.inv_m = p->inv_m.p;
+  g.sens_col = p->sens_col.p;
+  if (p->n_programs > 0) {
+    g.NW = p->n_custom_weights;
+    g.row_prog = p->row_prog.p; g.row_w0 = p->row_w0.p; g.prog_base = p->prog_base.p; g.prog_sub_off = p->prog_sub_off.p;
+    g.prog_code = p->prog_code.p; g.prog_const = p->prog_const.p; g.row_time = p->row_time.p;
+  }
+  return g;
 }
 
 static int project_run(sbm_project* p, const double* Theta, int V, const sbm_integrator_opts* opts, bool sens,
@@ -1202,27 +721,13 @@ static int project_run(sbm_project* p, const double* Theta, int V, const sbm_int
     SBM_HIP(hipGetLastError());
   }
 
-  AssembleArgs g;
-  memset(&g, 0, sizeof(g));
-  g.E = p->E; g.q = p->q; g.R = p->R; g.G = p->G; g.NPR = p->NPR; g.NSP = p->NSP; g.NP = NP; g.NV = NV; g.NK = NK; g.n_t = nt;
-  g.compat = p->compat;
-  g.loss = p->loss;
-  g.row_exp = p->row_exp.p; g.row_tidx = p->row_tidx.p; g.row_var_off = p->row_var_off.p; g.row_vars = p->row_vars.p;
-  g.row_sf = p->row_sf.p; g.prior_idx = p->prior_idx.p; g.row_data = p->row_data.p; g.row_sigma = p->row_sigma.p;
-  g.prior_mean = p->prior_mean.p; g.prior_sigma = p->prior_sigma.p;
-  g.sfp_group = p->sfp_group.p; g.sfp_mean = p->sfp_mean.p; g.sfp_sigma = p->sfp_sigma.p; g.inv_ptr = p->inv_ptr.p; g.inv_m = p->inv_m.p;
-  g.sens_col = p->sens_col.p;
-  if (p->n_programs > 0) {
-    g.NW = p->n_custom_weights;
-    g.row_prog = p->row_prog.p; g.row_w0 = p->row_w0.p; g.prog_base = p->prog_base.p; g.prog_sub_off = p->prog_sub_off.p;
-    g.prog_code = p->prog_code.p; g.prog_const = p->prog_const.p; g.row_time = p->row_time.p;
-  }
+  AssembleArgs g = assemble_args(p);
   g.Theta = Theta; g.Y = p->Y.p; g.S = sens ? p->S.p : nullptr;
   g.traj_status = p->traj_status.p; g.traj_steps = p->traj_steps.p;
   g.sims = sims ? sims : p->sims.p; g.Rout = Rout; g.sf = sf; g.norms = norms; g.status = status; g.n_steps = n_steps;
   g.J = sens ? J : nullptr; g.Jmodel = sens ? Jmodel : nullptr; g.grad = sens ? grad : nullptr;
   g.sf_grad = sens ? sf_grad : nullptr;
-  return launch_assemble(m->ctx, g, V, s, who);
+  return launch_assemble(m->ctx, g, V, who);
 }
 
 extern "C" int sbm_residuals_batch(sbm_project* p, const double* Theta, int32_t V, const sbm_integrator_opts* opts,
@@ -1245,94 +750,69 @@ extern "C" int sbm_jacobian_batch(sbm_project* p, const double* Theta, int32_t V
 // Loss functions on caller-supplied simulations (the reference's frame-level API, a13):
 // the same assembly kernel, reading sims / the model Jacobian from the caller instead of Y / S.
 // ---------------------------------------------------------------------------------------------
+namespace {
+struct LossFrames {   // device copies of one sbm_loss_eval_host call
+  DevBuf<double> data, sigma, spm, sps, sims, Jm, R, J, sf, sfg, norms;
+  DevBuf<int32_t> sfi, plain, spg, status;
+};
+}  // namespace
+
+// uploads, the kernel and the copies back, all on the context's stream; returns at the first failure with whatever is
+// already enqueued still running on `b`
+static int loss_eval_enqueue(sbm_ctx* ctx, const sbm_loss_desc* d, int V, const double* sims, const double* Jm, double* Rout,
+                             double* J, double* sf, double* sf_grad, double* norms, int32_t* status, LossFrames& b,
+                             const char* who) {
+  hipStream_t s = ctx->stream;
+  const int R = d->n_rows, q = d->n_params, G = d->n_sf_groups, NSP = d->n_sf_prior_rows;
+  const int RT = R + NSP, qq = q > 0 ? q : 1;
+  int bad = 0;
+  bad |= upload(b.data, d->row_data, (size_t)R, s);
+  bad |= upload(b.sigma, d->row_sigma, (size_t)R, s);
+  bad |= upload(b.sfi, d->row_sf, (size_t)R, s);
+  if (d->row_plain) bad |= upload(b.plain, d->row_plain, (size_t)R, s);
+  bad |= upload(b.spg, d->sf_prior_group, (size_t)NSP, s);
+  bad |= upload(b.spm, d->sf_prior_mean, (size_t)NSP, s);
+  bad |= upload(b.sps, d->sf_prior_sigma, (size_t)NSP, s);
+  bad |= upload(b.sims, sims, (size_t)V * R, s);
+  if (Jm) bad |= upload(b.Jm, Jm, (size_t)V * R * q, s);
+  bad |= b.R.reserve((size_t)V * RT) | b.sf.reserve((size_t)V * (G ? G : 1)) | b.norms.reserve(V) | b.status.reserve(V);
+  if (J) bad |= b.J.reserve((size_t)V * RT * qq);
+  if (Jm) bad |= b.sfg.reserve((size_t)V * (G ? G : 1) * qq);
+  if (bad) return sbm_fail(SBM_E_HIP, "%s: device allocation / upload failed", who);
+  AssembleArgs g;
+  memset(&g, 0, sizeof(g));
+  g.E = 1; g.q = qq; g.R = R; g.G = G; g.NPR = 0; g.NSP = NSP;
+  g.compat = d->reference_compat; g.loss = d->loss_type;
+  g.row_sf = b.sfi.p; g.row_data = b.data.p; g.row_sigma = b.sigma.p; g.row_plain = d->row_plain ? b.plain.p : nullptr;
+  g.sfp_group = b.spg.p; g.sfp_mean = b.spm.p; g.sfp_sigma = b.sps.p;
+  g.sims_in = b.sims.p; g.Jm_in = Jm ? b.Jm.p : nullptr;
+  g.Rout = b.R.p; g.sf = b.sf.p; g.norms = b.norms.p; g.status = b.status.p;
+  g.J = J ? b.J.p : nullptr; g.sf_grad = Jm ? b.sfg.p : nullptr;
+  if (int rc = launch_assemble(ctx, g, V, who)) return rc;
+  hipError_t e = hipMemcpyAsync(Rout, b.R.p, (size_t)V * RT * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && J) e = hipMemcpyAsync(J, b.J.p, (size_t)V * RT * q * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && sf && G) e = hipMemcpyAsync(sf, b.sf.p, (size_t)V * G * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && sf_grad && G) e = hipMemcpyAsync(sf_grad, b.sfg.p, (size_t)V * G * q * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && norms) e = hipMemcpyAsync(norms, b.norms.p, (size_t)V * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && status) e = hipMemcpyAsync(status, b.status.p, (size_t)V * 4, hipMemcpyDeviceToHost, s);
+  if (e != hipSuccess) return sbm_fail(SBM_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  return 0;
+}
+
 extern "C" int sbm_loss_eval_host(sbm_ctx* ctx, const sbm_loss_desc* d, int32_t V, const double* sims, const double* Jm,
                                   double* Rout, double* J, double* sf, double* sf_grad, double* norms, int32_t* status) {
   const char* who = "sbm_loss_eval_host";
   if (!ctx || !d || !sims || !Rout) return sbm_fail(SBM_E_ARG, "%s: NULL argument", who);
-  const int R = d->n_rows, q = d->n_params, G = d->n_sf_groups, NSP = d->n_sf_prior_rows;
-  if (V < 0 || R <= 0 || q < 0 || G < 0 || NSP < 0) return sbm_fail(SBM_E_ARG, "%s: bad sizes V=%d R=%d q=%d G=%d", who, V, R, q, G);
-  if (d->loss_type != SBM_LOSS_SQUARE && d->loss_type != SBM_LOSS_LOG_SQUARE)
-    return sbm_fail(SBM_E_ARG, "%s: unknown loss_type %d", who, d->loss_type);
-  if (!d->row_data || !d->row_sigma || !d->row_sf) return sbm_fail(SBM_E_ARG, "%s: NULL array in descriptor", who);
-  if ((J || sf_grad) && (!Jm || q <= 0)) return sbm_fail(SBM_E_ARG, "%s: J / sf_grad need the model Jacobian", who);
-  if (NSP && (!d->sf_prior_group || !d->sf_prior_mean || !d->sf_prior_sigma)) return sbm_fail(SBM_E_ARG, "%s: NULL sf prior array", who);
-  for (int r = 0; r < R; ++r) {
-    if (d->row_sf[r] >= G) return sbm_fail(SBM_E_ARG, "%s: row %d sf group %d", who, r, d->row_sf[r]);
-    const bool plain = d->row_plain && d->row_plain[r];
-    if (plain && d->row_sf[r] >= 0) return sbm_fail(SBM_E_ARG, "%s: plain row %d cannot carry a scale factor", who, r);
-    if (d->loss_type == SBM_LOSS_LOG_SQUARE && !plain && !(d->row_data[r] > 0.0))
-      return sbm_fail(SBM_E_ARG, "%s: LogSquare loss cannot handle measurements smaller or equal to zero (row %d)", who, r);
-  }
-  for (int k = 0; k < NSP; ++k)
-    if (d->sf_prior_group[k] < 0 || d->sf_prior_group[k] >= G) return sbm_fail(SBM_E_ARG, "%s: sf prior group", who);
+  if (int rc = sbm_loss_desc_check(d, V, Jm != nullptr, J || sf_grad, who, g_err, sizeof(g_err))) return rc;
   if (V == 0) return 0;
   SBM_HIP(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  const int RT = R + NSP, qq = q > 0 ? q : 1;
-  DevBuf<double> b_data, b_sigma, b_spm, b_sps, b_sims, b_Jm, b_R, b_J, b_sf, b_sfg, b_norms;
-  DevBuf<int32_t> b_sfi, b_plain, b_spg, b_status;
-  int bad = 0;
-  bad |= upload(b_data, d->row_data, (size_t)R, s);
-  bad |= upload(b_sigma, d->row_sigma, (size_t)R, s);
-  bad |= upload(b_sfi, d->row_sf, (size_t)R, s);
-  if (d->row_plain) bad |= upload(b_plain, d->row_plain, (size_t)R, s);
-  bad |= upload(b_spg, d->sf_prior_group, (size_t)NSP, s);
-  bad |= upload(b_spm, d->sf_prior_mean, (size_t)NSP, s);
-  bad |= upload(b_sps, d->sf_prior_sigma, (size_t)NSP, s);
-  bad |= upload(b_sims, sims, (size_t)V * R, s);
-  if (Jm) bad |= upload(b_Jm, Jm, (size_t)V * R * q, s);
-  bad |= b_R.reserve((size_t)V * RT) | b_sf.reserve((size_t)V * (G ? G : 1)) | b_norms.reserve(V) | b_status.reserve(V);
-  if (J) bad |= b_J.reserve((size_t)V * RT * qq);
-  if (Jm) bad |= b_sfg.reserve((size_t)V * (G ? G : 1) * qq);
-  int rc = 0;
-  if (bad) rc = sbm_fail(SBM_E_HIP, "%s: device allocation / upload failed", who);
-  if (!rc) {
-    AssembleArgs g;
-    memset(&g, 0, sizeof(g));
-    g.E = 1; g.q = qq; g.R = R; g.G = G; g.NPR = 0; g.NSP = NSP;
-    g.compat = d->reference_compat; g.loss = d->loss_type;
-    g.row_sf = b_sfi.p; g.row_data = b_data.p; g.row_sigma = b_sigma.p; g.row_plain = d->row_plain ? b_plain.p : nullptr;
-    g.sfp_group = b_spg.p; g.sfp_mean = b_spm.p; g.sfp_sigma = b_sps.p;
-    g.sims_in = b_sims.p; g.Jm_in = Jm ? b_Jm.p : nullptr;
-    g.Rout = b_R.p; g.sf = b_sf.p; g.norms = b_norms.p; g.status = b_status.p;
-    g.J = J ? b_J.p : nullptr; g.sf_grad = Jm ? b_sfg.p : nullptr;
-    rc = launch_assemble(ctx, g, V, s, who);
-  }
-  hipError_t e = hipSuccess;
-  if (!rc) {
-    e = hipMemcpyAsync(Rout, b_R.p, (size_t)V * RT * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && J) e = hipMemcpyAsync(J, b_J.p, (size_t)V * RT * q * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && sf && G) e = hipMemcpyAsync(sf, b_sf.p, (size_t)V * G * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && sf_grad && G) e = hipMemcpyAsync(sf_grad, b_sfg.p, (size_t)V * G * q * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && norms) e = hipMemcpyAsync(norms, b_norms.p, (size_t)V * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && status) e = hipMemcpyAsync(status, b_status.p, (size_t)V * 4, hipMemcpyDeviceToHost, s);
-  }
-  hipError_t e2 = hipStreamSynchronize(s);
-  b_data.release(); b_sigma.release(); b_spm.release(); b_sps.release(); b_sims.release(); b_Jm.release(); b_R.release();
-  b_J.release(); b_sf.release(); b_sfg.release(); b_norms.release(); b_sfi.release(); b_plain.release(); b_spg.release();
-  b_status.release();
-  if (rc) return rc;
-  if (e != hipSuccess || e2 != hipSuccess) return sbm_fail(SBM_E_HIP, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : e2));
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Kernels with dynamic LDS: what a workgroup may have, and the launch.
-// ---------------------------------------------------------------------------------------------
-static int lm_lds_limit(sbm_ctx* ctx) {
-  int lim = 0;
-  if (hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess || lim <= 0) lim = 64 * 1024;
-  return lim;
-}
-
-// `kernel` on the context's device and stream with `lds` bytes of dynamic LDS; more than 64 KB have to be asked for
-template <class... P, class... A>
-static int launch_lds(sbm_ctx* ctx, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, const A&... args) {
-  SBM_HIP(hipSetDevice(ctx->device));
-  if (lds > 64 * 1024) SBM_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, args...);
-  SBM_HIP(hipGetLastError());
-  return 0;
+  // The frames outlive everything enqueued on them: they are freed when this function returns, and however the
+  // enqueueing ended, the one return below comes after the stream has drained.
+  LossFrames b;
+  const int rc = loss_eval_enqueue(ctx, d, V, sims, Jm, Rout, J, sf, sf_grad, norms, status, b, who);
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (rc == 0 && e != hipSuccess) return sbm_fail(SBM_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  return rc;
 }
 
 // ---------------------------------------------------------------------------------------------

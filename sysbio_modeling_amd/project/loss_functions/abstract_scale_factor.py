@@ -2,7 +2,7 @@
 
 The reference keeps the arithmetic on these objects (project/loss_functions/abstract_scale_factor.py:6-42
 declares ``update_sf`` / ``update_sf_gradient`` / prior hooks for subclasses to fill in); here the
-arithmetic runs inside csrc/sbm_core.hip::k_assemble and the object is a plain record: the value B and
+arithmetic runs inside csrc/sbm_assemble.hpp::k_assemble and the object is a plain record: the value B and
 its gradient dB/dtheta as last written back by ``SquareLossFunction._store``, and the optional Gaussian
 prior on log B that ``Project.set_scale_factor_log_prior`` attaches.
 """

@@ -2,7 +2,7 @@
 
 The arithmetic of the reference's ``update_sf`` / ``update_sf_gradient``
 (project/loss_functions/squared_loss/linear_scale_factor.py:27-42) runs on the
-device inside csrc/sbm_core.hip::k_assemble; this object only carries the latest
+device inside csrc/sbm_assemble.hpp::k_assemble; this object only carries the latest
 values back to the caller (``Project.scale_factors[measure].sf``).
 """
 import numpy as np

@@ -2,7 +2,7 @@
 
 log B = sum(w (log d - log s)) / sum(w),  w = (d / sigma)^2
 (reference project/loss_functions/squared_loss/log_scale_factor.py:17-36; evaluated on the
-device in csrc/sbm_core.hip::k_assemble, this object carries the last values)."""
+device in csrc/sbm_assemble.hpp::k_assemble, this object carries the last values)."""
 from .linear_scale_factor import LinearScaleFactor
 
 

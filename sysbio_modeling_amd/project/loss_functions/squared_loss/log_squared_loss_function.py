@@ -1,5 +1,5 @@
 """r = (log(B sim) - log(data)) / sigma  (reference log_squared_loss_function.py:9-98).
-Configuration object: the arithmetic runs in csrc/sbm_core.hip::k_assemble (SBM_LOSS_LOG_SQUARE)."""
+Configuration object: the arithmetic runs in csrc/sbm_assemble.hpp::k_assemble (SBM_LOSS_LOG_SQUARE)."""
 from .squared_loss_function import SquareLossFunction
 from .log_scale_factor import LogScaleFactor
 

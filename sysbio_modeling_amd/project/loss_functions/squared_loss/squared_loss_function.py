@@ -1,7 +1,7 @@
 """Weighted squared loss with optional linear scale factors.
 
 Configuration object for the loss the assembly kernel evaluates
-(csrc/sbm_core.hip::k_assemble):  r = (B s - d) / sigma,  J = B dS + s (x) dB
+(csrc/sbm_assemble.hpp::k_assemble):  r = (B s - d) / sigma,  J = B dS + s (x) dB
 (reference project/loss_functions/squared_loss/squared_loss_function.py:27-80,
 abstract_loss_function.py:22-120).  It holds the scale-factor groups, their
 priors and the last values computed on the device.

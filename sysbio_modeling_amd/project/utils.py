@@ -4,7 +4,7 @@
 scale-factor groups (project/utils.py:98-158, pinned by tests/test_Project_Utils.py).
 The reference's four sampling functions (project/utils.py:10-89) have no Python
 counterpart here: 'direct' / 'sum' sampling runs inside the fused assembly kernel
-(csrc/sbm_core.hip::k_assemble); ``sample_index`` is the one piece of them the
+(csrc/sbm_assemble.hpp::k_assemble); ``sample_index`` is the one piece of them the
 host needs -- which grid points the kernels must land on.
 """
 from collections import OrderedDict

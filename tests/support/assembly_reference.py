@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE -- the assembly kernel's arithmetic restated in extended precision.
 
-What ``k_assemble`` (csrc/sbm_core.hip) returns for one parameter vector -- simulations per row, model Jacobian, scale
+What ``k_assemble`` (csrc/sbm_assemble.hpp) returns for one parameter vector -- simulations per row, model Jacobian, scale
 factors and their gradient, residuals, Jacobian, sum of squares, gradient -- written from the formulas of include/sbm.h
 (sbm_project_desc / sbm_loss_desc) and oracle/project_oracle.py, in numpy ``longdouble`` (64-bit mantissa) or, where the
 platform's long double is no wider than a double, in mpmath at 40 digits.  Nothing here is taken from the kernel: no

@@ -1,4 +1,4 @@
-"""The assembly kernel (k_assemble, csrc/sbm_core.hip) at every edge of its layout, against the wide reference of
+"""The assembly kernel (k_assemble, csrc/sbm_assemble.hpp) at every edge of its layout, against the wide reference of
 tests/support/assembly_reference.py -- plain sums in numpy longdouble from the formulas of include/sbm.h and
 oracle/project_oracle.py, errors normalised by each output's scale and bounded by C(n) u (derived there).
 
