@@ -138,11 +138,11 @@ def plugin_path(name):
 def build_plugin(name, header_path, force=False, extra_flags=()):
     """sbm_model_<name>.so from a generated model header."""
     os.makedirs(BUILD_DIR, exist_ok=True)
-    # developer A/B builds: SBM_PLUGIN_FLAGS="-DFOO=1" compiles a separately named plugin
-    env_flags = tuple(os.environ.get('SBM_PLUGIN_FLAGS', '').split())
-    if env_flags:
-        name = name + '_' + hashlib.sha1(' '.join(env_flags).encode()).hexdigest()[:8]
-        extra_flags = tuple(extra_flags) + env_flags
+    # A/B builds: extra_flags=('-DFOO=1',) or SBM_PLUGIN_FLAGS="-DFOO=1" compiles a separately named plugin, the same
+    # one either way (e.g. -DSBM_RG_EARLY_STAGES=0: the row-group kernels without the early operand fetch)
+    extra_flags = tuple(extra_flags) + tuple(os.environ.get('SBM_PLUGIN_FLAGS', '').split())
+    if extra_flags:
+        name = name + '_' + hashlib.sha1(' '.join(extra_flags).encode()).hexdigest()[:8]
     out = plugin_path(name)
     # every header of csrc/ goes into the stamp (round 4 added one and the explicit list missed it: stale plugins)
     srcs = [header_path, os.path.join(CSRC_DIR, 'sbm_plugin_main.hip')] + \

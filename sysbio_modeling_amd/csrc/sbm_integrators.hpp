@@ -226,6 +226,26 @@ constexpr double E3_1 = -0.18980075407240762, E3_6 = 4.450312892752409, E3_7 = 1
     sys.finish(tok_, (tt), zt, kout);       \
   }
 #define SBM_STAGE(tt, stmt, kout) SBM_ISSUE(tt, stmt) SBM_STAGE_THEN(tt, stmt, kout, )
+// The same with the stage's number s (sbm_dopri45: 2..7).  A System that has eval_stage<s> decides per stage how much
+// of the hand-over eval starts (RowGroupSystem: whether the operand fetch of finish is issued there already); the
+// token's type tells extra_out / finish what it carries.  Every other System is called through its one eval.
+template <int S, class Sys, class P>
+__device__ __forceinline__ auto sbm_stage_eval(const Sys& sys, const P& p, double t, int)
+    -> decltype(sys.template eval_stage<S>(p, t)) {
+  return sys.template eval_stage<S>(p, t);
+}
+template <int S, class Sys, class P>
+__device__ __forceinline__ auto sbm_stage_eval(const Sys& sys, const P& p, double t, long) {
+  return sys.eval(p, t);
+}
+#define SBM_STAGE_THEN_N(s, tt, stmt, kout, next)            \
+  {                                                          \
+    auto tok_ = sbm_stage_eval<s>(sys, pend_, (tt), 0);      \
+    sys.extra_out(tok_, kout);                               \
+    next                                                     \
+    SBM_MAIN(c, i) { stmt }                                  \
+    sys.finish(tok_, (tt), zt, kout);                        \
+  }
 
 // ---------------------------------------------------------------------------
 // "System" policies: what differs between the two mappings
@@ -517,15 +537,15 @@ __device__ __forceinline__ SbmTrajOut sbm_dopri45(const Sys& sys, double (&z)[Sy
 #define SBM_P6 if constexpr (kFold) { ha65 = hs * A65; ha75 = hs * A75; }
 #define SBM_P7 if constexpr (kFold) { ha76 = hs * A76; }
       SBM_ISSUE(t + C2 * hs, SBM_S2)
-      SBM_STAGE_THEN(t + C2 * hs, SBM_S2, k2, SBM_P3 SBM_ISSUE(t + C3 * hs, SBM_S3))
-      SBM_STAGE_THEN(t + C3 * hs, SBM_S3, k3, SBM_P4 SBM_ISSUE(t + C4 * hs, SBM_S4))
-      SBM_STAGE_THEN(t + C4 * hs, SBM_S4, k4, SBM_P5 SBM_ISSUE(t + C5 * hs, SBM_S5))
-      SBM_STAGE_THEN(t + C5 * hs, SBM_S5, k5, SBM_P6 SBM_ISSUE(t + hs, SBM_S6))
-      SBM_STAGE_THEN(t + hs, SBM_S6, k6, SBM_P7 SBM_ISSUE(t + hs, SBM_S7))
+      SBM_STAGE_THEN_N(2, t + C2 * hs, SBM_S2, k2, SBM_P3 SBM_ISSUE(t + C3 * hs, SBM_S3))
+      SBM_STAGE_THEN_N(3, t + C3 * hs, SBM_S3, k3, SBM_P4 SBM_ISSUE(t + C4 * hs, SBM_S4))
+      SBM_STAGE_THEN_N(4, t + C4 * hs, SBM_S4, k4, SBM_P5 SBM_ISSUE(t + C5 * hs, SBM_S5))
+      SBM_STAGE_THEN_N(5, t + C5 * hs, SBM_S5, k5, SBM_P6 SBM_ISSUE(t + hs, SBM_S6))
+      SBM_STAGE_THEN_N(6, t + hs, SBM_S6, k6, SBM_P7 SBM_ISSUE(t + hs, SBM_S7))
       // zt is the 5th-order solution now.  k1 was last read when the input of stage 5 was formed, so
       // k7 = f(z_new) goes straight into it: an accepted step continues with it (FSAL, no copy), a
       // rejected one -- rare -- re-evaluates f(z).  One stage vector fewer alive through stages 5-7.
-      SBM_STAGE_THEN(t + hs, SBM_S7, k1, )
+      SBM_STAGE_THEN_N(7, t + hs, SBM_S7, k1, )
 #undef SBM_S2
 #undef SBM_S3
 #undef SBM_S4
@@ -1425,10 +1445,13 @@ struct SbmRowGroupShared {
   alignas(16) double H[L::RG_RPG * LS + 4];        // published rows of the stage vector (+ zero slot)
 };
 
-// EARLY: fetch the lane's A / J_y operands right after the row lanes published them (eval) instead of
-// in finish, so that the column rows of the stage vector are formed while they are in flight.  Costs
-// 2*(NV + RPG*JYS) more live VGPRs: pays for RK4 (18.0 vs 19.4 ms), spills for DOPRI45 (20.7 vs 7.5 ms).
-template <class M, class L, bool EARLY>
+// Early hand-over: fetch the lane's A / J_y operands right after the row lanes published them (eval) instead of
+// in finish, so that the column rows of the stage vector are formed while they are in flight.  The token carries
+// them from eval to finish: 2*(NV + RPG*JYS) more live VGPRs across the stage argument.
+//   EARLY         every stage, numbered or not (RK4: 18.0 vs 19.4 ms);
+//   EARLY_STAGES  bit s set: stage s of a driver that numbers its stages (sbm_dopri45, 2..7) fetches early; the
+//                 unnumbered eval / rhs (first evaluation, reject path) follow EARLY alone.  See SBM_RG_EARLY_STAGES.
+template <class M, class L, bool EARLY, unsigned EARLY_STAGES = 0u>
 struct RowGroupSystem {
   static constexpr int G = L::RG_G, C = L::RG_C, RPG = L::RG_RPG;
   static constexpr int NV = L::RG_RPG * L::RG_CPL;   // elements of S this lane integrates
@@ -1452,10 +1475,13 @@ struct RowGroupSystem {
   double* h_lane;
   int hoff[NH];
 
-  struct Token {
+  template <bool E>
+  struct TokenT {   // E: the operands travel with it
+    static constexpr bool kEarly = E;
     double f[RPL];
-    double acol[EARLY ? NV : 1], coef[EARLY ? RPG * L::RG_JYS : 1];
+    double acol[E ? NV : 1], coef[E ? RPG * L::RG_JYS : 1];
   };
+  using Token = TokenT<EARLY>;
   struct Pending { double ys[RPL][M::RL_MAXYS]; };
   __device__ __forceinline__ Pending issue(double /*t*/, const double (&z)[1][NVX]) const {
     Pending p;
@@ -1469,8 +1495,14 @@ struct RowGroupSystem {
     SBM_LDS_FENCE();
     return p;
   }
-  __device__ __forceinline__ Token eval(const Pending& p, double t) const {
-    Token k;
+  __device__ __forceinline__ Token eval(const Pending& p, double t) const { return eval_as<EARLY>(p, t); }
+  template <int S>
+  __device__ __forceinline__ TokenT<EARLY || ((EARLY_STAGES >> S) & 1u)> eval_stage(const Pending& p, double t) const {
+    return eval_as<EARLY || ((EARLY_STAGES >> S) & 1u)>(p, t);
+  }
+  template <bool E>
+  __device__ __forceinline__ TokenT<E> eval_as(const Pending& p, double t) const {
+    TokenT<E> k;
     double jy[RPL][M::RL_MAXJY], jp[RPL][M::RL_MAXJP];
 #pragma unroll
     for (int r = 0; r < RPL; ++r) {
@@ -1491,20 +1523,21 @@ struct RowGroupSystem {
       for (int s = 0; s < M::RL_MAXJY; ++s) sh->JYL[jypos[r][s]] = jy[r][s];
     }
     SBM_LDS_FENCE();
-    if constexpr (EARLY) {
+    if constexpr (E) {
       L::load_rowgroup(a_lane, jy_lane, k.acol, k.coef);
       SBM_LDS_FENCE();
     }
     return k;
   }
-  __device__ __forceinline__ void finish(const Token& k, double /*t*/, const double (&z)[1][NVX],
+  template <class Tok>
+  __device__ __forceinline__ void finish(const Tok& k, double /*t*/, const double (&z)[1][NVX],
                                          double (&dz)[1][NVX]) const {
     double zc[NV], dc[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) zc[i] = z[0][i];
     L::publish_rowgroup(h_lane, zc);
     SBM_LDS_FENCE();
-    if constexpr (EARLY) {
+    if constexpr (Tok::kEarly) {
       L::apply_rowgroup(k.acol, k.coef, sh->H, hoff, zc, dc);
     } else {
       double acol[NV], coef[RPG * L::RG_JYS];
@@ -1515,7 +1548,8 @@ struct RowGroupSystem {
 #pragma unroll
     for (int i = 0; i < NV; ++i) dz[0][i] = dc[i];
   }
-  __device__ __forceinline__ void extra_out(const Token& k, double (&dz)[1][NVX]) const {
+  template <class Tok>
+  __device__ __forceinline__ void extra_out(const Tok& k, double (&dz)[1][NVX]) const {
 #pragma unroll
     for (int r = 0; r < RPL; ++r) dz[0][NV + r] = k.f[r];
   }
@@ -1549,6 +1583,13 @@ struct RowGroupSystem {
   __device__ __forceinline__ double sum(double v) const { return sbm_wave_sum(v); }
 };
 
+// the layouts whose DOPRI45 stages fetch early by default (derivation: at SBM_RG_EARLY_DEFAULT below)
+template <class M, class L>
+constexpr bool sbm_rg_early_fits() {
+  constexpr int elems = L::RG_RPG * L::RG_CPL, rpl = (M::NV + 63) / 64;
+  return rpl == 1 ? elems <= 14 : (rpl == 2 && elems <= 7);
+}
+
 template <class M, class L, int METHOD>
 // Two waves per SIMD (256 registers each) when the lane's share of S is small enough for DOPRI45's seven
 // stage vectors to fit: 2*(RPG*CPL + 1)*7 + operands <= 256 holds up to 15 elements (cascade20: 14 + 1).
@@ -1557,8 +1598,34 @@ template <class M, class L, int METHOD>
 #define SBM_RG_MIN_WAVES (METHOD == SBM_DOP853 ? ((L::RG_RPG * L::RG_CPL + (M::NV + 63) / 64 <= 8) ? 2 : 1) \
                           : ((L::RG_RPG * L::RG_CPL + (M::NV + 63) / 64 <= 15 || METHOD == SBM_RK4_FIXED) ? 2 : 1))
 #endif
+// Which stages of DOPRI45 (bit s = stage s, 2..7) fetch their operands early (RowGroupSystem::eval_stage).
+// -DSBM_RG_EARLY_STAGES=<mask> sets it for every layout (0: every stage fetches in finish, the schedule before the
+// switch existed); without it the default applies where the layout leaves room for the operands:
+//   * Since the running-sum form of sbm_dopri45 seven stage vectors are alive at the peak and five by stage 7, and the
+//     14 + 14 operands of cascade20 / RG0 (14 elements + 1 state row, 256 VGPRs, two waves) fit next to them: with
+//     any mask the step loop stays free of scratch and vector memory, the loop body at 832 - 833 VALU instructions
+//     (837 with mask 0), vgpr_spill_count 24 -> 32, all outside the loop.
+//   * The default is stages 2, 3, 4 and 7, the ones with the smaller live set.  In stages 5 and 6 (six and seven
+//     stage vectors alive) the compiler answers an early fetch by forming the stage argument ABOVE it, so nothing is
+//     covered (VALU instructions between the last operand read and the wait that drains it, mask 0xFC against mask 0:
+//     stage 5 4 / 11, stage 6 16 / 26; stages 2, 3, 4, 7 of the default 13 / 2, 7 / 5, 19 / 4, 69 / 4), and pinning
+//     the order with __builtin_amdgcn_sched_barrier spills (126 VGPRs, 96 scratch instructions in the loop).
+//     MI355X, 4096 vectors, ms per pass: mask 0 and the commit before 8.97 - 9.02, 0x9C 8.84 - 8.96, 0xFC 8.82 -
+//     8.92: the two cannot be told apart, so the smaller one ships (docs/history.md, "Stage hand-over").
+//   * Counted in the ISA of the zoo plugins and of cascade40 / cascade70 / stiff80 built with mask 0xFC: with ONE
+//     state row per lane no layout gains scratch in its loop (cascade20 14 / 3 / 7 elements, cascade40 10 / 5 / 7,
+//     stiff50 9 / 7).  With TWO state rows per lane (two row evaluations and their tables alive per stage) the
+//     layouts of 6 and 7 elements stay clean (cascade70 / RG2, stiff80 / RG1) and those of 10 and 12 do not:
+//     cascade70 / RG0 70 and RG1 39, stiff80 / RG0 34 scratch instructions inside the step loop, none before.
+//   * Layouts of more than 14 elements (one wave per SIMD) have not been looked at: off.
+#define SBM_RG_EARLY_DEFAULT 0x9Cu
+#ifdef SBM_RG_EARLY_STAGES
+#define SBM_RG_EARLY_MASK ((unsigned)(SBM_RG_EARLY_STAGES))
+#else
+#define SBM_RG_EARLY_MASK (sbm_rg_early_fits<M, L>() ? SBM_RG_EARLY_DEFAULT : 0u)
+#endif
 __global__ void __launch_bounds__(64, SBM_RG_MIN_WAVES) sbm_sens_rowgroup_kernel(sbm_kernel_args a) {
-  using Sys = RowGroupSystem<M, L, METHOD == SBM_RK4_FIXED>;
+  using Sys = RowGroupSystem<M, L, METHOD == SBM_RK4_FIXED, METHOD == SBM_DOPRI45 ? SBM_RG_EARLY_MASK : 0u>;
   using Sh = SbmRowGroupShared<M, L>;
   constexpr int MNV = M::NV, NK = M::NK;
   constexpr int G = L::RG_G, C = L::RG_C, RPG = L::RG_RPG, CPL = L::RG_CPL;
