@@ -6,7 +6,7 @@ Builds the project from synthetic data (5 % noise), runs Levenberg-Marquardt fro
 starts at once, then walks 64 Metropolis chains from the best fit, once with the host sampler (candidates and
 acceptance in numpy around one batched device evaluation per step), once with sampler='device' (the whole step
 enqueued on the device, one synchronisation at the end) and once with sampler='device_recalc' (the reference's second
-algorithm on the device: every chain's candidate from the Hessian at its own point, Metropolis-Hastings acceptance), and turns the sampled ensemble into the 95 % band of one scaled
+algorithm on the device: every chain's candidate from the Hessian at its own point, Metropolis-Hastings acceptance; then once more with half of the parameters held and the others in a box), and turns the sampled ensemble into the 95 % band of one scaled
 observable (trajectories of all members, then mean / sd / quantiles over the members on the device).  Everything the loops evaluate -- ODEs, forward
 sensitivities, scale factors, residuals, Jacobians, normal equations -- runs on the device."""
 import os
@@ -60,6 +60,16 @@ def main():
     loose = np.argsort(sd)[-3:]
     print("    best constrained (log-units sd): " + ", ".join("%s %.3f" % (names[i], sd[i]) for i in tight))
     print("    sloppiest:                       " + ", ".join("%s %.3f" % (names[i], sd[i]) for i in loose))
+    # the same sampler on the problem a bounded fit with held parameters poses: the sloppier half of the parameters stays at
+    # the fit, the others stay inside fit +- 3 (a uniform prior on the box).  Every chain's eigen-problem is the 34 x 34 one
+    # of its free parameters, and a candidate outside the box is never integrated.
+    held = np.argsort(sd)[-34:]
+    box = (fit['theta'][best] - 3.0, fit['theta'][best] + 3.0)
+    ensemble_log_params_batch(proj, start, steps=2, sampler='device_recalc', held=held, bounds=box, **chains)
+    t0 = time.time()
+    ens_b, _, ratio_b = ensemble_log_params_batch(proj, start, steps=200, sampler='device_recalc', held=held, bounds=box, **chains)
+    print("MCMC (device_recalc, 34 of %d held, bounds = fit +- 3): 64 chains x 200 steps in %.2f s, acceptance %.2f; held "
+          "parameters moved by %.1g" % (ens.shape[-1], time.time() - t0, ratio_b.mean(), np.abs(ens_b[:, :, held] - start[:, held]).max()))
     # predictions with uncertainty: the chains after burn-in, (n_kept, C, q) as the sampler returns them
     times = np.linspace(0.0, 100.0, 201)
     t0 = time.time()

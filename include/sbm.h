@@ -543,6 +543,17 @@ int sbm_project_sf_entropy(sbm_project* project, const double* sims_dev, int32_t
 int sbm_mh_propose(sbm_ctx* ctx, const double* curr_dev, const double* samp_dev, int32_t per_chain, const double* z_dev,
                    int32_t C, int32_t q, double* trial_dev);
 
+/* sbm_mh_propose inside a box and with held components (project/ensembles.py `held=` / `bounds=`).  held [C][q] (nullable):
+ * != 0 = the component is a copy of curr, no arithmetic; lower, upper [C][q] (nullable, together; +-inf leaves a side open).
+ * A free component is curr_i + sum_j samp_ij z_j by sbm_mh_propose's chain of fmas: the same bits.  If any free component t
+ * of chain c fails t >= lower && t <= upper (a bound itself is inside, a NaN is not) the whole row of trial is a copy of
+ * curr -- a point that is known to integrate -- and outside[c] = 1, else 0: the veto of sbm_mh_accept[_hastings]_ex.
+ * A chain with every component held has no candidate: outside[c] = 1 too (it stays put and counts no accepted move).
+ * One wavefront per chain.  trial must not be curr.  An added export: SBM_ABI_VERSION is unchanged. */
+int sbm_mh_propose_box(sbm_ctx* ctx, const double* curr_dev, const double* samp_dev, int32_t per_chain, const double* z_dev,
+                       int32_t C, int32_t q, const int32_t* held_dev, const double* lower_dev, const double* upper_dev,
+                       double* trial_dev, int32_t* outside_dev);
+
 /* Metropolis rule for C chains: F_trial = 0.5 norms_trial - entropy_trial (entropy_trial NULL: energy 0.5 |r|^2); the
  * trial point is taken iff status_trial == 0, F_trial is finite and log_u < -(F_trial - F_curr) / T.  Taken points
  * replace curr and F_curr and count in n_accepted; ens_slot [C][q] and ens_F_slot [C] (nullable) receive the chains'
@@ -551,6 +562,12 @@ int sbm_mh_accept(sbm_ctx* ctx, const double* norms_trial_dev, const int32_t* st
                   const double* entropy_trial_dev, const double* log_u_dev, double temperature, int32_t C, int32_t q,
                   const double* trial_dev, double* curr_dev, double* F_curr_dev, int32_t* n_accepted_dev,
                   double* ens_slot_dev, double* ens_F_slot_dev);
+/* The same with veto [C] (nullable): a chain with veto != 0 is not moved, whatever its energy.  NULL: sbm_mh_accept.
+ * An added export: SBM_ABI_VERSION is unchanged. */
+int sbm_mh_accept_ex(sbm_ctx* ctx, const double* norms_trial_dev, const int32_t* status_trial_dev,
+                     const double* entropy_trial_dev, const double* log_u_dev, double temperature, int32_t C, int32_t q,
+                     const double* trial_dev, double* curr_dev, double* F_curr_dev, int32_t* n_accepted_dev,
+                     double* ens_slot_dev, double* ens_F_slot_dev, const int32_t* veto_dev);
 
 /* ---- the sampler's second algorithm (project/ensembles.py, sampler='device_recalc') ---- */
 /* Axes of the Gaussian candidate density from a Hessian per chain (the reference's _sampling_matrix, Ensembles.py:226-258,
@@ -578,6 +595,20 @@ int sbm_sampling_axes(sbm_ctx* ctx, const double* J_dev, const double* row_scale
                       int32_t per_chain_H, int32_t C, int32_t M, int32_t q, double cutoff, double temperature,
                       double step_scale, double* eig_dev, double* V_dev, double* s_dev, double* samp_dev,
                       int32_t* status_dev);
+/* The same in the subspace of every chain's free parameters: held [C][q], != 0 = the column takes no part (NULL:
+ * sbm_sampling_axes, the same kernel).  With f_0 < ... < f_{nf-1} the free columns of chain c, the kernel gathers J[:, f]
+ * (or H[f][:, f]) and is from there on sbm_sampling_axes on that nf x nf problem -- the same sums in the same order, so the
+ * reduced outputs have the bits of sbm_sampling_axes on the arrays with the held columns deleted, and n_eff and
+ * cutoff max a are the reduced problem's; a held entry of J or H is not looked at, finite or not.  Outputs in the full layout:
+ *   eig[c][i], s[c][i]   the reduced values for i < nf; eig = 0, s = 1 for i >= nf
+ *   V[c][f_k][i]         V_reduced[k][i] for k, i < nf; 0 in the held rows and in the columns >= nf; samp alike
+ * so sbm_mh_propose[_box] leaves held components where they are, and the padding adds u = 0 and log 1 = 0 to the candidate
+ * density of sbm_mh_accept_hastings[_ex], which is then the reduced problem's.  nf = 0: status 0 with the padding alone.
+ * Status 1 as in sbm_sampling_axes, on all q entries.  An added export: SBM_ABI_VERSION is unchanged. */
+int sbm_sampling_axes_held(sbm_ctx* ctx, const double* J_dev, const double* row_scale_dev, const double* H_dev,
+                           int32_t per_chain_H, int32_t C, int32_t M, int32_t q, double cutoff, double temperature,
+                           double step_scale, double* eig_dev, double* V_dev, double* s_dev, double* samp_dev,
+                           int32_t* status_dev, const int32_t* held_dev);
 
 /* Metropolis-Hastings rule for C chains whose candidate density depends on the point (the reference's
  * _accept_move_recalc_alg, Ensembles.py:200-224).  The arguments of sbm_mh_accept, then the axes of the candidate density at
@@ -594,6 +625,15 @@ int sbm_mh_accept_hastings(sbm_ctx* ctx, const double* norms_trial_dev, const in
                            double* s_curr_dev, double* samp_curr_dev, const double* V_trial_dev,
                            const double* s_trial_dev, const double* samp_trial_dev,
                            const int32_t* axes_status_trial_dev);
+/* The same with veto [C] (nullable) as in sbm_mh_accept_ex; the axes status of a vetoed chain is not looked at.
+ * An added export: SBM_ABI_VERSION is unchanged. */
+int sbm_mh_accept_hastings_ex(sbm_ctx* ctx, const double* norms_trial_dev, const int32_t* status_trial_dev,
+                              const double* entropy_trial_dev, const double* log_u_dev, double temperature, int32_t C,
+                              int32_t q, const double* trial_dev, double* curr_dev, double* F_curr_dev,
+                              int32_t* n_accepted_dev, double* ens_slot_dev, double* ens_F_slot_dev, double* V_curr_dev,
+                              double* s_curr_dev, double* samp_curr_dev, const double* V_trial_dev,
+                              const double* s_trial_dev, const double* samp_trial_dev,
+                              const int32_t* axes_status_trial_dev, const int32_t* veto_dev);
 
 /* ---- ensemble predictions: statistics over the member axis ------------------ */
 /* replaces traj_ensemble_stats / traj_ensemble_quantiles / the NaN filter of few_ensemble_trajs

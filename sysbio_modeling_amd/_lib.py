@@ -106,6 +106,12 @@ SIGNATURES = {
     'sbm_project_sf_entropy': (ctypes.c_int, [_vp, _vp, _i32, ctypes.c_double, _vp, _vp]),
     'sbm_mh_propose': (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp]),
     'sbm_mh_accept': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sbm_mh_propose_box': (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'sbm_mh_accept_ex': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sbm_sampling_axes_held': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sbm_mh_accept_hastings_ex': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sbm_sampling_axes': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.c_double, ctypes.c_double,
                                          ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
     'sbm_mh_accept_hastings': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -12,10 +12,10 @@
 //                           sbm_loss_eval_host verify of a descriptor before they touch the device (plain C++, no HIP)
 //   sbm_lm.hpp              k_lm_step, k_lm_trust[_held|_bounded], k_lm_update, k_lm_accept: the fitting loop (batched Levenberg-Marquardt
 //                           step, lmder's trust-region step and bookkeeping)
-//   sbm_sampler.hpp         k_sf_entropy, k_mh_propose, k_mh_accept, k_mh_accept_hastings: scale-factor entropy integrals
+//   sbm_sampler.hpp         k_sf_entropy, k_mh_propose[_box], k_mh_accept, k_mh_accept_hastings: scale-factor entropy integrals
 //                           (linear_scale_factor.py:63-81; the quadrature rule: sbm_sf_quadrature.hpp), candidate move and
 //                           the two acceptance rules of the multi-chain sampler (project/Ensembles.py:193-198, 200-264)
-//   sbm_sampling_axes.hpp   k_sampling_axes: per-chain Hessian axes (batched Jacobi eigensolver + SloppyCell's clipping
+//   sbm_sampling_axes.hpp   k_sampling_axes[_held]: per-chain Hessian axes (batched Jacobi eigensolver + SloppyCell's clipping
 //                           recipe; project/Ensembles.py:153-157)
 //   sbm_ensemble_stats.hpp  k_ens_*: statistics over the member axis of an ensemble of trajectories
 //                           (project/Ensembles.py:277-308, 335-361)
@@ -955,24 +955,51 @@ extern "C" int sbm_mh_propose(sbm_ctx* ctx, const double* curr, const double* sa
   return 0;
 }
 
-extern "C" int sbm_mh_accept(sbm_ctx* ctx, const double* norms_trial, const int32_t* status_trial, const double* entropy_trial,
-                             const double* log_u, double temperature, int32_t C, int32_t q, const double* trial, double* curr,
-                             double* F_curr, int32_t* n_accepted, double* ens_slot, double* ens_F_slot) {
+extern "C" int sbm_mh_propose_box(sbm_ctx* ctx, const double* curr, const double* samp, int32_t per_chain, const double* z, int32_t C,
+                                  int32_t q, const int32_t* held, const double* lower, const double* upper, double* trial,
+                                  int32_t* outside) {
+  if (!ctx || !curr || !samp || !z || !trial || !outside) return sbm_fail(SBM_E_ARG, "sbm_mh_propose_box: NULL argument");
+  if ((lower == nullptr) != (upper == nullptr)) return sbm_fail(SBM_E_ARG, "sbm_mh_propose_box: lower and upper go together");
+  if (trial == curr) return sbm_fail(SBM_E_ARG, "sbm_mh_propose_box: trial must not be curr");
+  if (C < 0 || q <= 0) return sbm_fail(SBM_E_ARG, "sbm_mh_propose_box: bad sizes C=%d q=%d", C, q);
+  if (C == 0) return 0;
+  SBM_HIP(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(k_mh_propose_box, dim3((C + 3) / 4), dim3(256), 0, ctx->stream, curr, samp, per_chain, z, C, q, held, lower, upper,
+                     trial, outside);
+  SBM_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int sbm_mh_accept_ex(sbm_ctx* ctx, const double* norms_trial, const int32_t* status_trial, const double* entropy_trial,
+                                const double* log_u, double temperature, int32_t C, int32_t q, const double* trial, double* curr,
+                                double* F_curr, int32_t* n_accepted, double* ens_slot, double* ens_F_slot, const int32_t* veto) {
   if (!ctx || !norms_trial || !status_trial || !log_u || !trial || !curr || !F_curr || !n_accepted)
     return sbm_fail(SBM_E_ARG, "sbm_mh_accept: NULL argument");
   if (C < 0 || q <= 0) return sbm_fail(SBM_E_ARG, "sbm_mh_accept: bad sizes C=%d q=%d", C, q);
   if (!(temperature > 0.0)) return sbm_fail(SBM_E_ARG, "sbm_mh_accept: temperature must be positive");
   if (C == 0) return 0;
-  sbm_mh_args a{norms_trial, status_trial, entropy_trial, log_u, temperature, C, q, trial, curr, F_curr, n_accepted, ens_slot, ens_F_slot};
+  sbm_mh_args a{norms_trial, status_trial, entropy_trial, log_u, temperature, C, q, trial, curr, F_curr, n_accepted, ens_slot, ens_F_slot,
+                veto};
   SBM_HIP(hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_mh_accept, dim3((C + 3) / 4), dim3(256), 0, ctx->stream, a);
   SBM_HIP(hipGetLastError());
   return 0;
 }
 
-extern "C" int sbm_sampling_axes(sbm_ctx* ctx, const double* J, const double* row_scale, const double* H, int32_t per_chain_H,
-                                 int32_t C, int32_t M, int32_t q, double cutoff, double temperature, double step_scale,
-                                 double* eig, double* V, double* s, double* samp, int32_t* status) {
+extern "C" int sbm_mh_accept(sbm_ctx* ctx, const double* norms_trial, const int32_t* status_trial, const double* entropy_trial,
+                             const double* log_u, double temperature, int32_t C, int32_t q, const double* trial, double* curr,
+                             double* F_curr, int32_t* n_accepted, double* ens_slot, double* ens_F_slot) {
+  return sbm_mh_accept_ex(ctx, norms_trial, status_trial, entropy_trial, log_u, temperature, C, q, trial, curr, F_curr, n_accepted,
+                          ens_slot, ens_F_slot, nullptr);
+}
+
+// held = NULL: k_sampling_axes, as before sbm_sampling_axes_held existed; otherwise k_sampling_axes_held, whose static LDS
+// (the list of free columns and the waves' counts, read from the code object) has to fit the workgroup together with the
+// dynamic block: the same dynamic size, since the free columns are at most q.
+static_assert(AXES_MAX_Q == SBM_SAMPLING_AXES_MAX_Q, "the index list of k_sampling_axes_held holds SBM_SAMPLING_AXES_MAX_Q columns");
+extern "C" int sbm_sampling_axes_held(sbm_ctx* ctx, const double* J, const double* row_scale, const double* H, int32_t per_chain_H,
+                                      int32_t C, int32_t M, int32_t q, double cutoff, double temperature, double step_scale,
+                                      double* eig, double* V, double* s, double* samp, int32_t* status, const int32_t* held) {
   if (!ctx || !status) return sbm_fail(SBM_E_ARG, "sbm_sampling_axes: NULL argument");
   if ((J == nullptr) == (H == nullptr)) return sbm_fail(SBM_E_ARG, "sbm_sampling_axes: exactly one of J and H must be given");
   if (H && row_scale) return sbm_fail(SBM_E_ARG, "sbm_sampling_axes: row_scale goes with J");
@@ -987,14 +1014,30 @@ extern "C" int sbm_sampling_axes(sbm_ctx* ctx, const double* J, const double* ro
   if (lds > (size_t)lm_lds_limit(ctx))
     return sbm_fail(SBM_E_ARG, "sbm_sampling_axes: q = %d does not fit the %d KB of LDS of a workgroup", q, lm_lds_limit(ctx) / 1024);
   sbm_axes_args a{J, row_scale, H, per_chain_H, M, q, cutoff, temperature, step_scale, eig, V, s, samp, status};
-  return launch_lds(ctx, k_sampling_axes, dim3(C), dim3(256), lds, a);
+  if (!held) return launch_lds(ctx, k_sampling_axes, dim3(C), dim3(256), lds, a);
+  static const size_t stat = [] {   // asked once: the kernel is the same on every device
+    hipFuncAttributes fa;
+    return hipFuncGetAttributes(&fa, (const void*)k_sampling_axes_held) == hipSuccess ? (size_t)fa.sharedSizeBytes : (size_t)256;
+  }();
+  if (lds + stat > (size_t)lm_lds_limit(ctx))
+    return sbm_fail(SBM_E_ARG, "sbm_sampling_axes: q = %d does not fit the %d KB of LDS of a workgroup (%zu B + %zu B static)", q,
+                    lm_lds_limit(ctx) / 1024, lds, stat);
+  return launch_lds(ctx, k_sampling_axes_held, dim3(C), dim3(256), lds, a, held);
 }
 
-extern "C" int sbm_mh_accept_hastings(sbm_ctx* ctx, const double* norms_trial, const int32_t* status_trial,
-                                      const double* entropy_trial, const double* log_u, double temperature, int32_t C, int32_t q,
-                                      const double* trial, double* curr, double* F_curr, int32_t* n_accepted, double* ens_slot,
-                                      double* ens_F_slot, double* V_curr, double* s_curr, double* samp_curr, const double* V_trial,
-                                      const double* s_trial, const double* samp_trial, const int32_t* axes_status_trial) {
+extern "C" int sbm_sampling_axes(sbm_ctx* ctx, const double* J, const double* row_scale, const double* H, int32_t per_chain_H,
+                                 int32_t C, int32_t M, int32_t q, double cutoff, double temperature, double step_scale,
+                                 double* eig, double* V, double* s, double* samp, int32_t* status) {
+  return sbm_sampling_axes_held(ctx, J, row_scale, H, per_chain_H, C, M, q, cutoff, temperature, step_scale, eig, V, s, samp, status,
+                                nullptr);
+}
+
+extern "C" int sbm_mh_accept_hastings_ex(sbm_ctx* ctx, const double* norms_trial, const int32_t* status_trial,
+                                         const double* entropy_trial, const double* log_u, double temperature, int32_t C, int32_t q,
+                                         const double* trial, double* curr, double* F_curr, int32_t* n_accepted, double* ens_slot,
+                                         double* ens_F_slot, double* V_curr, double* s_curr, double* samp_curr, const double* V_trial,
+                                         const double* s_trial, const double* samp_trial, const int32_t* axes_status_trial,
+                                         const int32_t* veto) {
   if (!ctx || !norms_trial || !status_trial || !log_u || !trial || !curr || !F_curr || !n_accepted || !V_curr || !s_curr ||
       !samp_curr || !V_trial || !s_trial || !samp_trial || !axes_status_trial)
     return sbm_fail(SBM_E_ARG, "sbm_mh_accept_hastings: NULL argument");
@@ -1004,8 +1047,18 @@ extern "C" int sbm_mh_accept_hastings(sbm_ctx* ctx, const double* norms_trial, c
   const size_t lds = sizeof(double) * (size_t)q;
   if (lds > (size_t)lm_lds_limit(ctx)) return sbm_fail(SBM_E_ARG, "sbm_mh_accept_hastings: q = %d does not fit the LDS of a workgroup", q);
   sbm_mh_hastings_args a{{norms_trial, status_trial, entropy_trial, log_u, temperature, C, q, trial, curr, F_curr, n_accepted,
-                          ens_slot, ens_F_slot}, V_curr, s_curr, samp_curr, V_trial, s_trial, samp_trial, axes_status_trial};
+                          ens_slot, ens_F_slot, veto}, V_curr, s_curr, samp_curr, V_trial, s_trial, samp_trial, axes_status_trial};
   return launch_lds(ctx, k_mh_accept_hastings, dim3(C), dim3(256), lds, a);
+}
+
+extern "C" int sbm_mh_accept_hastings(sbm_ctx* ctx, const double* norms_trial, const int32_t* status_trial,
+                                      const double* entropy_trial, const double* log_u, double temperature, int32_t C, int32_t q,
+                                      const double* trial, double* curr, double* F_curr, int32_t* n_accepted, double* ens_slot,
+                                      double* ens_F_slot, double* V_curr, double* s_curr, double* samp_curr, const double* V_trial,
+                                      const double* s_trial, const double* samp_trial, const int32_t* axes_status_trial) {
+  return sbm_mh_accept_hastings_ex(ctx, norms_trial, status_trial, entropy_trial, log_u, temperature, C, q, trial, curr, F_curr,
+                                   n_accepted, ens_slot, ens_F_slot, V_curr, s_curr, samp_curr, V_trial, s_trial, samp_trial,
+                                   axes_status_trial, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // sbm_sampler.hpp -- kernels of the Metropolis sampler's step on the device (project/ensembles.py, sampler='device' and
 // 'device_recalc'): scale-factor entropy of the trial simulations (sbm_project_sf_entropy; the quadrature rule itself is
-// sbm_sf_quadrature.hpp, which is also compiled for the host), candidate move (sbm_mh_propose), and the two acceptance
-// rules (sbm_mh_accept, sbm_mh_accept_hastings).  Between sbm_mh_propose, sbm_residuals_batch, sbm_project_sf_entropy
+// sbm_sf_quadrature.hpp, which is also compiled for the host), candidate move (sbm_mh_propose; inside a box and with held
+// components: sbm_mh_propose_box), and the two acceptance rules (sbm_mh_accept[_ex], sbm_mh_accept_hastings[_ex]).  Between sbm_mh_propose, sbm_residuals_batch, sbm_project_sf_entropy
 // and the acceptance no number goes through the host.  The host wrappers with the argument checks are in sbm_core.hip.
 #ifndef SBM_SAMPLER_HPP
 #define SBM_SAMPLER_HPP
@@ -78,6 +78,41 @@ __global__ void __launch_bounds__(256) k_mh_propose(const double* __restrict__ c
   trial[idx] = curr[idx] + d;
 }
 
+// The candidate move inside a box and with held components (sbm_mh_propose_box).  One wavefront per chain, four chains per
+// workgroup; the lanes stride over the components.  A free component is curr_i + sum_j samp_ij z_j by k_mh_propose's chain
+// of fmas in k_mh_propose's order (the same bits); a held one is curr_i, no arithmetic.  If any free component is not
+// inside [lower, upper] -- a NaN is not -- the whole row becomes curr again, a point that is known to integrate, and
+// outside[c] = 1 tells the acceptance kernel (veto) that the chain does not move.  A chain with nothing free has no
+// candidate: outside[c] = 1 as well, so that it counts no accepted move.  held, lower / upper nullable.
+__global__ void __launch_bounds__(256) k_mh_propose_box(const double* __restrict__ curr, const double* __restrict__ samp, int per_chain,
+                                                        const double* __restrict__ z, int C, int q, const int32_t* __restrict__ held,
+                                                        const double* __restrict__ lower, const double* __restrict__ upper,
+                                                        double* __restrict__ trial, int32_t* __restrict__ outside) {
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (c >= C) return;
+  const size_t o1 = (size_t)c * q;
+  const double* sc = samp + (per_chain ? o1 * q : 0);
+  const double* zc = z + o1;
+  int out = 0, moves = 0;
+  for (int i = lane; i < q; i += 64) {
+    double t = curr[o1 + i];
+    if (!(held && held[o1 + i] != 0)) {
+      moves = 1;
+      const double* row = sc + (size_t)i * q;
+      double d = 0.0;
+      for (int j = 0; j < q; ++j) d = fma(row[j], zc[j], d);
+      t += d;
+      const double lo = lower ? lower[o1 + i] : -__builtin_inf(), hi = upper ? upper[o1 + i] : __builtin_inf();
+      out |= !(t >= lo && t <= hi);
+    }
+    trial[o1 + i] = t;
+  }
+  out = __any(out) || !__any(moves);
+  if (out)
+    for (int i = lane; i < q; i += 64) trial[o1 + i] = curr[o1 + i];
+  if (lane == 0) outside[c] = out ? 1 : 0;
+}
+
 // What the two acceptance rules have in common: the chains' state and the trial points
 struct sbm_mh_args {
   const double* norms_t;       // [C]
@@ -92,12 +127,13 @@ struct sbm_mh_args {
   int32_t* n_accepted;         // [C]       in / out
   double* ens_slot;            // [C][q]    nullable
   double* ens_F_slot;          // [C]       nullable
+  const int32_t* veto;         // [C]       nullable: != 0 = the chain stays, whatever its energy (sbm_mh_propose_box's outside)
 };
 
-// free energy of chain c's trial point; false if the chain cannot move there (integration failed, not finite)
+// free energy of chain c's trial point; false if the chain cannot move there (integration failed, not finite, vetoed)
 __device__ __forceinline__ bool mh_trial_energy(const sbm_mh_args& a, int c, double* Ft) {
   *Ft = 0.5 * a.norms_t[c] - (a.entropy_t ? a.entropy_t[c] : 0.0);
-  return a.status_t[c] == 0 && is_finite(*Ft);
+  return a.status_t[c] == 0 && is_finite(*Ft) && !(a.veto && a.veto[c] != 0);
 }
 
 // the decided move of chain c, by the `nt` threads t = 0 .. nt - 1 that serve the chain: they stride over the q

@@ -21,6 +21,7 @@
 // LDS: A and V at leading dimension q + 1 -- the passes map consecutive lanes to consecutive columns, so the padding only
 // matters to the sign scan down a column -- plus 5 q doubles and 2 q ints: 153 600 bytes at q = SBM_SAMPLING_AXES_MAX_Q = 96.
 // No arrays in registers, no scratch.
+// k_sampling_axes_held (sbm_sampling_axes_held) is the same body on the free columns of every chain: see sampling_axes_body.
 #ifndef SBM_SAMPLING_AXES_HPP
 #define SBM_SAMPLING_AXES_HPP
 
@@ -51,9 +52,53 @@ static inline size_t sbm_axes_lds_bytes(int q) {
   return sizeof(double) * (2 * (size_t)q * ld + 2 * np + 4 * (size_t)q) + sizeof(int) * (2 * np + (size_t)q);
 }
 
-__global__ void __launch_bounds__(256) k_sampling_axes(sbm_axes_args a) {
+// HELD = false is sbm_sampling_axes: q = qf, column c is column c.  HELD = true (sbm_sampling_axes_held): the free columns
+// f_0 < ... < f_{q-1} of the chain (held[c][j] == 0) are listed in LDS by a ballot per wave, J's row tile (or H's rows and
+// columns) is gathered through the list, and from there on the kernel IS the HELD = false kernel on the q x q problem
+// (leading dimension q + 1, the same sums in the same order: the same bits as sbm_sampling_axes on the arrays with the
+// held columns deleted; a held entry is never read), until the outputs are scattered back into the full qf layout:
+// row f_k of V and samp holds row k of the reduced ones in its first q columns, everything else is 0, and eig = 0, s = 1
+// from position q on -- axes along which sbm_mh_propose does not move and which add u = 0, log 1 = 0 to the candidate
+// density of sbm_mh_accept_hastings.  Nothing free: status 0 with that padding alone.
+constexpr int AXES_MAX_Q = 96;                 // SBM_SAMPLING_AXES_MAX_Q of include/sbm.h
+template <bool HELD>
+__device__ __forceinline__ void sampling_axes_body(sbm_axes_args a, const int32_t* held) {
   extern __shared__ __attribute__((aligned(16))) double ax_smem[];
-  const int c = blockIdx.x, tid = threadIdx.x, q = a.q, ld = q + 1;
+  const int c = blockIdx.x, tid = threadIdx.x, qf = a.q;
+  int q = qf;                                  // order of the system that is solved
+  [[maybe_unused]] const short* idx = nullptr;
+  if constexpr (HELD) {
+    // the free columns in ascending order: a ballot per wave (qf <= 96: waves 0 and 1 have columns), the waves' counts in LDS
+    __shared__ short s_idx[AXES_MAX_Q];
+    __shared__ int s_cnt[4];
+    const bool is_free = tid < qf && held[(size_t)c * qf + tid] == 0;
+    const unsigned long long m = __ballot(is_free);
+    const int lane = tid & 63, wave = tid >> 6;
+    if (lane == 0) s_cnt[wave] = __popcll(m);
+    __syncthreads();
+    int base = 0;
+    for (int w = 0; w < wave; ++w) base += s_cnt[w];
+    q = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    if (is_free) s_idx[base + __popcll(m & ((1ull << lane) - 1ull))] = (short)tid;
+    // the padding: held rows of V and samp, and the axes from q on
+    for (int e = tid; e < qf * qf; e += 256) {
+      if (held[(size_t)c * qf + e / qf] == 0) continue;
+      if (a.V) a.V[(size_t)c * qf * qf + e] = 0.0;
+      if (a.samp) a.samp[(size_t)c * qf * qf + e] = 0.0;
+    }
+    for (int i = q + tid; i < qf; i += 256) {
+      if (a.eig) a.eig[(size_t)c * qf + i] = 0.0;
+      if (a.s) a.s[(size_t)c * qf + i] = 1.0;
+    }
+    if (q == 0) {                              // (uniform)
+      if (tid == 0) a.status[c] = 0;
+      return;
+    }
+    __syncthreads();
+    idx = s_idx;
+  }
+  auto col = [&](int k) -> int { if constexpr (HELD) return idx[k]; else return k; };   // column of J / H behind column k
+  const int ld = q + 1;
   const int ne = (q + 1) & ~1, np = ne / 2, nr = ne - 1;      // players, pairs of a round, rounds of a sweep
   double* A = ax_smem;                         // [q][ld]
   double* Vm = A + (size_t)q * ld;             // [q][ld]  eigenvectors in the columns; before that the row tile of J
@@ -72,7 +117,7 @@ __global__ void __launch_bounds__(256) k_sampling_axes(sbm_axes_args a) {
   // ---- 1. A = H / 2
   if (a.J) {
     const int M = a.M, TILE = q < 32 ? q : 32;
-    const double* Jc = a.J + (size_t)c * M * q;
+    const double* Jc = a.J + (size_t)c * M * qf;
     double* T = Vm;
     for (int e = tid; e < qq; e += 256) A[(e / q) * ld + e % q] = 0.0;
     for (int m0 = 0; m0 < M; m0 += TILE) {
@@ -80,7 +125,7 @@ __global__ void __launch_bounds__(256) k_sampling_axes(sbm_axes_args a) {
       __syncthreads();
       for (int e = tid; e < rows * q; e += 256) {
         const int rr = e / q, cc = e - rr * q;
-        double val = Jc[(size_t)(m0 + rr) * q + cc];
+        double val = Jc[(size_t)(m0 + rr) * qf + col(cc)];
         if (a.row_scale) val *= a.row_scale[m0 + rr];
         T[rr * ld + cc] = val;
         bad |= !is_finite(val);
@@ -101,10 +146,10 @@ __global__ void __launch_bounds__(256) k_sampling_axes(sbm_axes_args a) {
       bad |= !is_finite(v);
     }
   } else {
-    const double* Hc = a.H + (a.per_chain_H ? (size_t)c * qq : 0);
+    const double* Hc = a.H + (a.per_chain_H ? (size_t)c * qf * qf : 0);
     for (int e = tid; e < qq; e += 256) {
       const int i = e / q, j = e - i * q;
-      const double hij = Hc[(size_t)i * q + j], hji = Hc[(size_t)j * q + i];
+      const double hij = Hc[(size_t)col(i) * qf + col(j)], hji = Hc[(size_t)col(j) * qf + col(i)];
       const double v = 0.5 * (0.5 * hij + 0.5 * hji);
       A[i * ld + j] = v;
       bad |= !is_finite(hij) || !is_finite(v);
@@ -195,13 +240,13 @@ __global__ void __launch_bounds__(256) k_sampling_axes(sbm_axes_args a) {
 
   if (!converged) {
     const double nan = __builtin_nan("");
-    for (int e = tid; e < qq; e += 256) {
-      if (a.V) a.V[(size_t)c * qq + e] = 0.0;
-      if (a.samp) a.samp[(size_t)c * qq + e] = 0.0;
+    for (int e = tid; e < qf * qf; e += 256) {
+      if (a.V) a.V[(size_t)c * qf * qf + e] = 0.0;
+      if (a.samp) a.samp[(size_t)c * qf * qf + e] = 0.0;
     }
-    for (int i = tid; i < q; i += 256) {
-      if (a.eig) a.eig[(size_t)c * q + i] = nan;
-      if (a.s) a.s[(size_t)c * q + i] = nan;
+    for (int i = tid; i < qf; i += 256) {
+      if (a.eig) a.eig[(size_t)c * qf + i] = nan;
+      if (a.s) a.s[(size_t)c * qf + i] = nan;
     }
     if (tid == 0) a.status[c] = 1;
     return;
@@ -234,16 +279,32 @@ __global__ void __launch_bounds__(256) k_sampling_axes(sbm_axes_args a) {
       for (int j = 0; j < q; ++j) n_eff += fmin(av[j] / cut, 1.0);
     }
     sv[k] = a.step_scale * sqrt(a.temperature / n_eff) / sqrt(fmax(av[k], fmax(cut, DBL_MIN)));
-    if (a.eig) a.eig[(size_t)c * q + k] = av[k];
-    if (a.s) a.s[(size_t)c * q + k] = sv[k];
+    if (a.eig) a.eig[(size_t)c * qf + k] = av[k];
+    if (a.s) a.s[(size_t)c * qf + k] = sv[k];
   }
   __syncthreads();
-  for (int e = tid; e < qq; e += 256) {
-    const int r = e / q, k = e - r * q;
-    const int col = perm[k];
-    const double v = sg[col] * Vm[r * ld + col];
-    if (a.V) a.V[(size_t)c * qq + e] = v;
-    if (a.samp) a.samp[(size_t)c * qq + e] = v * sv[k];
+  if constexpr (HELD) {
+    // row f_r of the full layout: the reduced row in the first q columns, zeros behind it
+    for (int e = tid; e < q * qf; e += 256) {
+      const int r = e / qf, k = e - r * qf;
+      const size_t at = ((size_t)c * qf + idx[r]) * qf + k;
+      double v = 0.0, vs = 0.0;
+      if (k < q) {
+        const int from = perm[k];
+        v = sg[from] * Vm[r * ld + from];
+        vs = v * sv[k];
+      }
+      if (a.V) a.V[at] = v;
+      if (a.samp) a.samp[at] = vs;
+    }
+  } else {
+    for (int e = tid; e < qq; e += 256) {
+      const int r = e / q, k = e - r * q;
+      const int from = perm[k];
+      const double v = sg[from] * Vm[r * ld + from];
+      if (a.V) a.V[(size_t)c * qq + e] = v;
+      if (a.samp) a.samp[(size_t)c * qq + e] = v * sv[k];
+    }
   }
 #ifdef SBM_AXES_STATUS_CARRIES_SWEEPS
   if (tid == 0) a.status[c] = sweeps << 8;      // developer builds only: the sweep count for the measurements of docs/history.md
@@ -251,5 +312,10 @@ __global__ void __launch_bounds__(256) k_sampling_axes(sbm_axes_args a) {
   if (tid == 0) a.status[c] = 0;
 #endif
 }
+
+__global__ void __launch_bounds__(256) k_sampling_axes(sbm_axes_args a) { sampling_axes_body<false>(a, nullptr); }
+// held [C][q]: != 0 = the column takes no part.  Static LDS: 192 bytes of the index list + 16 of the waves' counts, which
+// the host wrapper adds to the dynamic block before it compares with the workgroup's limit.
+__global__ void __launch_bounds__(256) k_sampling_axes_held(sbm_axes_args a, const int32_t* held) { sampling_axes_body<true>(a, held); }
 
 #endif  // SBM_SAMPLING_AXES_HPP

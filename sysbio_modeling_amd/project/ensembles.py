@@ -26,9 +26,16 @@ import numpy as np
 from ._evaluation import DeviceEvaluator, finite_cost, inverse_row_sigma, one_device_call
 
 
-def sampling_axes(hessian, cutoff=0.0, temperature=1.0, step_scale=1.0):
+def sampling_axes(hessian, cutoff=0.0, temperature=1.0, step_scale=1.0, held=None):
     """Principal axes V (q, q) and step lengths s (q,) of the candidate density: a move is V @ (s * z), z standard
     normal.  ``hessian`` may carry leading batch axes (one Hessian per chain).
+
+    held : bool mask (q,), or (..., q) with batched Hessians (one mask per chain): the density lives in the subspace of the
+    free parameters -- the recipe below applied to the free x free block of the Hessian, i.e. the density conditional on
+    the held values -- and comes back in the padded full layout of ``sbm_sampling_axes_held`` (include/sbm.h): with nf free
+    parameters f_0 < ... < f_{nf-1}, V[f_k, i] and s[i] are the reduced problem's for k, i < nf; the held rows of V and its
+    columns from nf on are 0 and s = 1 there, so a move has no held component and ``_log_candidate_density`` is the reduced
+    problem's.
 
     The recipe is SloppyCell's, as the reference carries it (_sampling_matrix, Ensembles.py:226-258): along each
     principal axis v_i of A = hessian / 2 (eigenvalue a_i) the step has standard deviation 1 / sqrt(max(a_i, c)) with
@@ -37,6 +44,8 @@ def sampling_axes(hessian, cutoff=0.0, temperature=1.0, step_scale=1.0):
     expected quadratic cost increase of a move about 1, and multiplied by step_scale * sqrt(temperature).
     A is symmetric, so the axes come from ``eigh`` (the reference takes an SVD; the two agree up to the sign of each
     column, which a Gaussian candidate does not see)."""
+    if held is not None:
+        return _sampling_axes_held(np.asarray(hessian, dtype=float), cutoff, temperature, step_scale, held)
     A = 0.5 * np.asarray(hessian, dtype=float)
     a, V = np.linalg.eigh(0.5 * (A + np.swapaxes(A, -1, -2)))
     a = np.abs(a)                                   # singular values of a symmetric matrix
@@ -47,9 +56,35 @@ def sampling_axes(hessian, cutoff=0.0, temperature=1.0, step_scale=1.0):
     return V, step_scale * np.sqrt(temperature / n_eff) / np.sqrt(stiffness)
 
 
-def sampling_matrix(hessian, cutoff=0.0, temperature=1.0, step_scale=1.0):
-    """Candidate-move matrix M = V diag(s) of ``sampling_axes``: a move is M @ z, Gaussian with covariance M M^T."""
-    V, s = sampling_axes(hessian, cutoff, temperature, step_scale)
+def _sampling_axes_held(H, cutoff, temperature, step_scale, held):
+    """``sampling_axes`` with a mask: one ``eigh`` per distinct mask, on the free blocks of the Hessians that carry it"""
+    q = H.shape[-1]
+    mask = np.asarray(held)
+    if mask.dtype != np.bool_ or mask.shape[-1:] != (q,):
+        raise ValueError("held: a bool mask (q,) = (%d,) or one per Hessian (..., %d), not %s %s" % (q, q, mask.dtype, mask.shape))
+    try:
+        batch = np.broadcast_shapes(H.shape[:-2], mask.shape[:-1])
+    except ValueError:
+        raise ValueError("held: mask of shape %s does not go with Hessians of shape %s" % (mask.shape, H.shape)) from None
+    Hb = np.broadcast_to(H, batch + (q, q)).reshape(-1, q, q)
+    mb = np.broadcast_to(mask, batch + (q,)).reshape(-1, q)
+    V, s = np.zeros(Hb.shape), np.ones(mb.shape)
+    for m in np.unique(mb, axis=0):
+        rows = np.flatnonzero((mb == m).all(axis=1))
+        free = np.flatnonzero(~m)
+        nf = free.size
+        if nf == 0:
+            continue
+        Vr, sr = sampling_axes(Hb[rows][:, free][:, :, free], cutoff, temperature, step_scale)
+        V[rows[:, None, None], free[None, :, None], np.arange(nf)[None, None, :]] = Vr
+        s[rows[:, None], np.arange(nf)[None, :]] = sr
+    return V.reshape(batch + (q, q)), s.reshape(batch + (q,))
+
+
+def sampling_matrix(hessian, cutoff=0.0, temperature=1.0, step_scale=1.0, held=None):
+    """Candidate-move matrix M = V diag(s) of ``sampling_axes``: a move is M @ z, Gaussian with covariance M M^T
+    (``held``: in the free subspace, the held rows and the columns behind the free ones zero)."""
+    V, s = sampling_axes(hessian, cutoff, temperature, step_scale, held)
     return V * s[..., None, :]
 
 
@@ -71,7 +106,7 @@ def _log_candidate_density(step, V, s):
 
 def ensemble_log_params_batch(project, params, hess=None, steps=1000, temperature=1.0, step_scale=1.0,
                               sing_val_cutoff=0.0, seeds=None, skip_elems=0, energy='auto', recalc_hess_alg=False,
-                              sampler='host', draws=None, **integrator_overrides):
+                              sampler='host', draws=None, held=None, bounds=None, **integrator_overrides):
     """C Metropolis chains in log-parameter space, advanced together.
 
     params : (q,) start shared by all chains, or (C, q) one start per chain (``n_chains`` = C).
@@ -102,6 +137,20 @@ def ensemble_log_params_batch(project, params, hess=None, steps=1000, temperatur
     draws : (z, log_u) of shapes (steps, C, q) and (steps, C): the standard normal and log-uniform numbers to use
              instead of drawing them (the two device samplers only).  With 'device_recalc' the move is V (s z) with the
              eigenvectors signed as ``sbm_sampling_axes`` signs them (include/sbm.h).
+    held   : parameters that never move, in the forms of ``fit_batch(held=)`` (``fitting.normalize_held``: a bool mask (q,)
+             or (C, q) -- masks may differ from chain to chain --, indices, or (p_group, settings) pairs): every kept point has
+             the start's value there.  The candidate density lives in the free subspace (``sampling_axes(held=)``: the recipe
+             on the free x free block of the Hessian, n_eff and the cutoff those of the reduced problem).  A chain with
+             everything held is legal and stays put.  The samplers on the device compact every chain's eigen-problem to its
+             free columns (``sbm_sampling_axes_held``).
+    bounds : a box for the free parameters, in the forms of ``fit_batch(bounds=)`` (``fitting.normalize_bounds``; log units,
+             held columns exempt, a start outside its box raises the "infeasible" ValueError), as a uniform prior: a
+             candidate with a free component outside [lower, upper] (a bound itself is inside, a NaN is not) is rejected --
+             the exact Metropolis rule for the symmetric candidate of the first algorithm and the exact Metropolis-Hastings
+             rule for the second, the target being zero outside.  Such a chain evaluates its current point again in that
+             step's batched call (on the device: ``sbm_mh_propose_box`` puts it there and vetoes the chain in
+             ``sbm_mh_accept[_hastings]_ex``), so no launch waits for a trajectory outside the box and nothing is read back.
+             With both None every sampler makes the calls it made before these arguments existed.
     Returns (ens, ens_Fs, ratio): ens (n_kept, C, q) parameter sets including the starts, ens_Fs
     (n_kept, C) their energies, ratio (C,) accepted / attempted per chain.
     """
@@ -119,6 +168,13 @@ def ensemble_log_params_batch(project, params, hess=None, steps=1000, temperatur
         if q > _lib.SAMPLING_AXES_MAX_Q:
             raise ValueError("sampler='device_recalc': %d parameters; sbm_sampling_axes keeps the Hessian and its eigenvectors in "
                              "the LDS of one workgroup, which holds q <= %d (use sampler='host')" % (q, _lib.SAMPLING_AXES_MAX_Q))
+    box = None
+    if held is not None or bounds is not None:
+        from .fitting import normalize_bounds, normalize_held
+        held_m = normalize_held(held, C, q, project) if held is not None else np.zeros((C, q), dtype=bool)
+        lower, upper = (normalize_bounds(bounds, C, q, project, thetas0=starts, held=held_m) if bounds is not None
+                        else (np.full((C, q), -np.inf), np.full((C, q), np.inf)))
+        box = dict(held=held_m, lower=lower, upper=upper, any_held=held is not None, bounded=bounds is not None)
     sfs = list(project.scale_factors.values()) if project.scale_factors is not None else []
     if energy == 'auto':
         energy = 'free_energy' if sfs and all(sf.log_prior is not None for sf in sfs) else 'rss'
@@ -129,13 +185,19 @@ def ensemble_log_params_batch(project, params, hess=None, steps=1000, temperatur
         if recalc['hess'] is not None and recalc['hess'].shape != (q, q):
             raise ValueError("hess must have shape (%d, %d), not %s" % (q, q, recalc['hess'].shape))
         return _device_chains(project, starts, None, int(steps), float(temperature), seeds, int(skip_elems), energy, draws,
-                              integrator_overrides, recalc=recalc)
+                              integrator_overrides, recalc=recalc, box=box)
     if sampler == 'device':
         if hess is None:
             hess = _gauss_newton_hessians(project, starts[:1], inverse_row_sigma(project), integrator_overrides)[0]
-        return _device_chains(project, starts, sampling_matrix(hess, sing_val_cutoff, temperature, step_scale), int(steps),
-                              float(temperature), seeds, int(skip_elems), energy, draws, integrator_overrides)
+        if box is not None and box['any_held']:       # one matrix per chain: the masks may differ
+            samp = sampling_matrix(np.broadcast_to(np.asarray(hess, dtype=float), (C, q, q)), sing_val_cutoff, temperature,
+                                   step_scale, held=box['held'])
+        else:
+            samp = sampling_matrix(hess, sing_val_cutoff, temperature, step_scale)
+        return _device_chains(project, starts, samp, int(steps), float(temperature), seeds, int(skip_elems), energy, draws,
+                              integrator_overrides, box=box)
     rng = np.random.default_rng(seeds)
+    held_m = box['held'] if box is not None else None
 
     def F(th):
         if energy == 'free_energy':
@@ -154,7 +216,10 @@ def ensemble_log_params_batch(project, params, hess=None, steps=1000, temperatur
     curr_F = F(curr)
     if recalc_hess_alg:
         V, sv = sampling_axes(hessians(curr) if hess is None else np.broadcast_to(hess, (C, q, q)),
-                              sing_val_cutoff, temperature, step_scale)
+                              sing_val_cutoff, temperature, step_scale, held=held_m)
+    elif held_m is not None:
+        V, sv = sampling_axes(np.broadcast_to(np.asarray(hess, dtype=float), (C, q, q)), sing_val_cutoff, temperature,
+                              step_scale, held=held_m)
     else:
         V1, s1 = sampling_axes(hess, sing_val_cutoff, temperature, step_scale)
         V, sv = np.broadcast_to(V1, (C, q, q)), np.broadcast_to(s1, (C, q))
@@ -162,17 +227,28 @@ def ensemble_log_params_batch(project, params, hess=None, steps=1000, temperatur
     accepted = np.zeros(C)
     for step in range(1, int(steps) + 1):
         delta = np.einsum('cij,cj->ci', V, sv * rng.standard_normal((C, q)))     # _trial_move, one per chain
-        trial = curr + delta
+        if box is not None:
+            # held components stay; a candidate that left the box is rejected before F sees it: the chain's current
+            # point stands in, so the batch keeps its shape
+            delta = np.where(held_m, 0.0, delta)
+            trial = np.where(held_m, curr, curr + delta)
+            outside = (~((trial >= box['lower']) & (trial <= box['upper'])) & ~held_m).any(axis=1) | held_m.all(axis=1)
+            trial = np.where(outside[:, None], curr, trial)
+        else:
+            trial = curr + delta
         next_F = F(trial)
         log_ratio = -(next_F - curr_F) / temperature                               # _accept_move
         if recalc_hess_alg:
             ok = np.isfinite(next_F)
             # chains whose trial point cannot be integrated are rejected anyway: their Hessian is not needed
-            Vn, sn = sampling_axes(hessians(np.where(ok[:, None], trial, curr)), sing_val_cutoff, temperature, step_scale)
+            Vn, sn = sampling_axes(hessians(np.where(ok[:, None], trial, curr)), sing_val_cutoff, temperature, step_scale,
+                                   held=held_m)
             log_ratio = log_ratio + _log_candidate_density(-delta, Vn, sn) - _log_candidate_density(delta, V, sv)
         with np.errstate(over='ignore', invalid='ignore'):
             acc = np.log(rng.random(C)) < log_ratio
         acc &= np.isfinite(next_F)
+        if box is not None:
+            acc &= ~outside
         curr = np.where(acc[:, None], trial, curr)
         curr_F = np.where(acc, next_F, curr_F)
         if recalc_hess_alg:
@@ -188,7 +264,8 @@ def ensemble_log_params_batch(project, params, hess=None, steps=1000, temperatur
 _DRAW_BLOCK = 256      # steps whose random numbers are drawn at once
 
 
-def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems, energy, draws, overrides, recalc=None):
+def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems, energy, draws, overrides, recalc=None,
+                   box=None):
     """The loop of ``ensemble_log_params_batch(sampler='device')``: per step four enqueues on the context's stream and
     no read-back; the record is a preallocated device array that ``sbm_mh_accept`` writes every (skip_elems + 1)-th
     step.
@@ -196,7 +273,11 @@ def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems,
     With ``recalc`` = dict(hess, cutoff, step_scale) the loop of ``sampler='device_recalc'``: ``samp`` is not used, every
     chain keeps the axes (V, s, samp = V diag(s)) of its current point; per step five enqueues -- the evaluation is
     ``sbm_jacobian_batch``, ``sbm_sampling_axes`` turns the trial points' Jacobians into their axes, and
-    ``sbm_mh_accept_hastings`` decides with the candidate density at both ends and moves the axes with the point."""
+    ``sbm_mh_accept_hastings`` decides with the candidate density at both ends and moves the axes with the point.
+
+    With ``box`` = dict(held, lower, upper, ...) (``held=`` / ``bounds=``) the same enqueues in their box forms:
+    ``sbm_mh_propose_box`` (``samp`` (C, q, q) goes per chain), whose ``outside`` flags veto the chains in
+    ``sbm_mh_accept_ex`` / ``sbm_mh_accept_hastings_ex``, and ``sbm_sampling_axes_held`` on every chain's free columns."""
     import torch
     from .. import _lib
     ev = DeviceEvaluator(project)
@@ -228,6 +309,14 @@ def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems,
     jac = buf.get('jacobian')
     entropy = torch.empty((C,), dtype=f64, device=dev) if free else None
     n_acc = torch.zeros((C,), dtype=i32, device=dev)
+    held_d = lower_d = upper_d = outside = None
+    if box is not None:
+        if box['any_held']:
+            held_d = torch.from_numpy(np.ascontiguousarray(box['held'], dtype=np.int32)).to(dev)
+        if box['bounded']:
+            lower_d = torch.from_numpy(np.ascontiguousarray(box['lower'], dtype=np.float64)).to(dev)
+            upper_d = torch.from_numpy(np.ascontiguousarray(box['upper'], dtype=np.float64)).to(dev)
+        outside = torch.empty((C,), dtype=i32, device=dev)
     opts = None if host_loop else project._opts(**overrides)
 
     def evaluate(th):
@@ -249,6 +338,12 @@ def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems,
     def axes(out, hess=None):
         """V, s, samp of the points whose Jacobians ``evaluate`` left in ``jac`` (or of one Hessian for all chains)"""
         H = None if hess is None else torch.from_numpy(hess).to(dev)
+        if box is not None:
+            _lib.check(lib.sbm_sampling_axes_held(ctx.handle, p(jac) if H is None else None, p(row_scale) if H is None else None,
+                                                  p(H), 0, C, RT, q, recalc['cutoff'], temperature, recalc['step_scale'], None,
+                                                  p(out[0]), p(out[1]), p(out[2]), p(ax_status), p(held_d)),
+                       'sbm_sampling_axes_held')
+            return
         _lib.check(lib.sbm_sampling_axes(ctx.handle, p(jac) if H is None else None, p(row_scale) if H is None else None, p(H), 0,
                                          C, RT, q, recalc['cutoff'], temperature, recalc['step_scale'], None, p(out[0]),
                                          p(out[1]), p(out[2]), p(ax_status)), 'sbm_sampling_axes')
@@ -287,7 +382,11 @@ def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems,
                 z_blk = torch.randn((n, C, q), dtype=f64, device=dev, generator=gen)
                 u_blk = torch.log(torch.rand((n, C), dtype=f64, device=dev, generator=gen))
             z, log_u = z_blk[k], u_blk[k]
-        if recalc is None:
+        if box is not None:
+            m, per_chain = (samp_d, int(samp_d.dim() == 3)) if recalc is None else (ax_c[2], 1)
+            _lib.check(lib.sbm_mh_propose_box(ctx.handle, p(curr), p(m), per_chain, p(z), C, q, p(held_d), p(lower_d), p(upper_d),
+                                              p(trial), p(outside)), 'sbm_mh_propose_box')
+        elif recalc is None:
             _lib.check(lib.sbm_mh_propose(ctx.handle, p(curr), p(samp_d), 0, p(z), C, q, p(trial)), 'sbm_mh_propose')
         else:
             _lib.check(lib.sbm_mh_propose(ctx.handle, p(curr), p(ax_c[2]), 1, p(z), C, q, p(trial)), 'sbm_mh_propose')
@@ -295,10 +394,22 @@ def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems,
         slot = step // every if step % every == 0 else None
         if recalc is not None:
             axes(ax_t)
+            if box is not None:
+                _lib.check(lib.sbm_mh_accept_hastings_ex(ctx.handle, p(nr), p(st), p(entropy), p(log_u), temperature, C, q, p(trial),
+                                                         p(curr), p(F_curr), p(n_acc), p(ens[slot]) if slot is not None else None,
+                                                         p(ens_F[slot]) if slot is not None else None, p(ax_c[0]), p(ax_c[1]),
+                                                         p(ax_c[2]), p(ax_t[0]), p(ax_t[1]), p(ax_t[2]), p(ax_status), p(outside)),
+                           'sbm_mh_accept_hastings_ex')
+                continue
             _lib.check(lib.sbm_mh_accept_hastings(ctx.handle, p(nr), p(st), p(entropy), p(log_u), temperature, C, q, p(trial), p(curr),
                                                   p(F_curr), p(n_acc), p(ens[slot]) if slot is not None else None,
                                                   p(ens_F[slot]) if slot is not None else None, p(ax_c[0]), p(ax_c[1]), p(ax_c[2]),
                                                   p(ax_t[0]), p(ax_t[1]), p(ax_t[2]), p(ax_status)), 'sbm_mh_accept_hastings')
+            continue
+        if box is not None:
+            _lib.check(lib.sbm_mh_accept_ex(ctx.handle, p(nr), p(st), p(entropy), p(log_u), temperature, C, q, p(trial), p(curr),
+                                            p(F_curr), p(n_acc), p(ens[slot]) if slot is not None else None,
+                                            p(ens_F[slot]) if slot is not None else None, p(outside)), 'sbm_mh_accept_ex')
             continue
         _lib.check(lib.sbm_mh_accept(ctx.handle, p(nr), p(st), p(entropy), p(log_u), temperature, C, q, p(trial), p(curr),
                                      p(F_curr), p(n_acc), p(ens[slot]) if slot is not None else None,
