@@ -1451,6 +1451,9 @@ struct SbmRowGroupShared {
 //   EARLY         every stage, numbered or not (RK4: 18.0 vs 19.4 ms);
 //   EARLY_STAGES  bit s set: stage s of a driver that numbers its stages (sbm_dopri45, 2..7) fetches early; the
 //                 unnumbered eval / rhs (first evaluation, reject path) follow EARLY alone.  See SBM_RG_EARLY_STAGES.
+#ifndef SBM_RG_KEEP_F_SELECT
+#define SBM_RG_KEEP_F_SELECT 0
+#endif
 template <class M, class L, bool EARLY, unsigned EARLY_STAGES = 0u>
 struct RowGroupSystem {
   static constexpr int G = L::RG_G, C = L::RG_C, RPG = L::RG_RPG;
@@ -1461,6 +1464,11 @@ struct RowGroupSystem {
   static constexpr int NCS = L::RG_CPL;
   __device__ __forceinline__ static constexpr int col_of(int, int i) { return i / L::RG_RPG; }
   static constexpr int NH = L::RG_NHALO > 0 ? L::RG_NHALO : 1;
+  // M::RL_F_ZERO_OFF_ROW (emit_rowlane.py): every class body gives f == 0 exactly, through finite intermediates, when
+  // all its operands are 0.  Then a (lane, r) without a row is given ps = 0 and state operands that stay 0 by the
+  // kernel, and eval_as needs no select to keep its f at zero (2 v_cndmask_b32 per row evaluation).
+  // -DSBM_RG_KEEP_F_SELECT=1: the select everywhere, for A/B builds.
+  static constexpr bool kZeroOffRow = M::RL_F_ZERO_OFF_ROW && !SBM_RG_KEEP_F_SELECT;
   SbmRowGroupShared<M, L>* sh;
   int lane, grp, cp;             // lane = grp*C + cp on the active lanes
   int cbase;                     // first column of this wavefront's chunk
@@ -1512,7 +1520,9 @@ struct RowGroupSystem {
 #pragma unroll
       for (int s = 0; s < M::RL_MAXJP; ++s) jp[r][s] = 0.0;
       M::class_dispatch(cls[r], t, p.ys[r], ps[r], k.f[r], jy[r], jp[r]);
-      k.f[r] = cls[r] >= 0 ? k.f[r] : 0.0;   // lanes without a row come out of the select chain with the last class's value
+      // lanes without a row come out of the select chain with the last class's value: zero it, unless the class bodies
+      // do that themselves on the all-zero operands such lanes were given (kZeroOffRow)
+      if constexpr (!kZeroOffRow) k.f[r] = cls[r] >= 0 ? k.f[r] : 0.0;
     }
     SBM_LDS_FENCE();
 #pragma unroll
@@ -1665,6 +1675,17 @@ __global__ void __launch_bounds__(64, SBM_RG_MIN_WAVES) sbm_sens_rowgroup_kernel
     for (int s = 0; s < M::RL_MAXYS; ++s) sys.yidx[r][s] = M::rl_ys(s, row);
 #pragma unroll
     for (int s = 0; s < M::RL_MAXPS; ++s) sys.ps[r][s] = P[M::rl_ps(s, row)];
+    if constexpr (Sys::kZeroOffRow) {
+      // without a row: all-zero operands, so that f comes out of the class bodies as 0.  The state operands are read
+      // from the slot's own place in Y, which only ever receives this slot's state component: 0 from the start, and
+      // its derivative is the f in question.
+      if (!has_row) {
+#pragma unroll
+        for (int s = 0; s < M::RL_MAXYS; ++s) sys.yidx[r][s] = lane + 64 * r;
+#pragma unroll
+        for (int s = 0; s < M::RL_MAXPS; ++s) sys.ps[r][s] = 0.0;
+      }
+    }
 #pragma unroll
     for (int s = 0; s < M::RL_MAXJY; ++s) {
       const int jp_ = L::rg_jypos(s, row);

@@ -431,6 +431,73 @@ def choose_alignment(spec, d, make_printer):
     return best if cost(best) < plain else None
 
 
+def _class_cse(ci, canon, share_products):
+    """(temporaries, outputs) of class ``ci`` as ``class_dispatch`` prints them"""
+    repl, red = cse(list(canon), symbols=sympy.numbered_symbols('c%d_x' % ci), optimizations='basic')
+    if share_products:
+        repl, red = _share_products(repl, red, 'c%d_x' % ci)
+    return repl, red
+
+
+class _NotZero(Exception):
+    pass
+
+
+def _f_at_zero_operands(repl, f):
+    """Value of a class's ``f`` (with the temporaries ``repl`` it is printed with) when every state and parameter
+    operand is 0, found by walking the expression bottom-up in exact arithmetic.  Raises _NotZero where the walk cannot
+    vouch for the floating-point result: a node that is not finite (a reciprocal or logarithm of 0, 0/0), a dependence on
+    ``t``, or a sum with more than one non-zero term (zero would then rest on a cancellation that rounding may miss).
+    What is left is exact in floating point too: a product with a zero factor and finite others is 0, a sum of zeros
+    and at most one other term is that term."""
+    temps = {sym: e for sym, e in repl}
+    seen = {}
+
+    def value(node):
+        if node in seen:
+            return seen[node]
+        if isinstance(node, Symbol):
+            if node in temps:
+                v = value(temps[node])
+            elif node.name.startswith(('YS_', 'PS_')):
+                v = sympy.S.Zero
+            else:
+                raise _NotZero(node)
+        elif node.is_Atom:
+            v = node
+        else:
+            args = [value(a) for a in node.args]
+            if node.is_Add and sum(1 for a in args if a != 0) > 1:
+                raise _NotZero(node)
+            if getattr(node.func, '__name__', '') == 'SBM_RCP':      # (emit.py: b**(-n) is printed as SBM_RCP(b)**n)
+                v = sympy.Pow(args[0], -1)
+            elif isinstance(node, sympy.core.function.AppliedUndef):
+                raise _NotZero(node)
+            else:
+                v = node.func(*args)
+        if v.free_symbols or v.is_finite is not True:
+            raise _NotZero(node)
+        seen[node] = v
+        return v
+    return value(f)
+
+
+def f_zero_off_row(classes, share_products=False):
+    """Whether EVERY class body gives f == 0 exactly, with no 0/0 and no reciprocal of 0 on the way, when all its
+    parameter and state operands are 0 (``RL_F_ZERO_OFF_ROW`` of the model header).  The row-group kernels then give the
+    lanes that evaluate no row such operands instead of zeroing their f with a select after every evaluation.  Decided
+    on the expressions ``class_dispatch`` prints (the classes' CSE forms; a shared operation of the hoist is an operation
+    of each class it serves, on that class's operands)."""
+    for ci, c in enumerate(classes):
+        repl, red = _class_cse(ci, c['canon'], share_products)
+        try:
+            if _f_at_zero_operands(repl, red[0]) != 0:
+                return False
+        except _NotZero:
+            return False
+    return True
+
+
 def _dispatch_body(classes, n_slots, make_printer, hoist=True, share_products=False, memo=None):
     """The statements of ``class_dispatch``.  ``share_products``: a product that is a whole output of a class and also a
     group of factors of another of its outputs becomes a temporary of the class (``_share_products``)."""
@@ -455,9 +522,7 @@ def _dispatch_body(classes, n_slots, make_printer, hoist=True, share_products=Fa
         key = (ci, canon, share_products)
         if memo is not None and key in memo:
             return memo[key]
-        repl, red = cse(list(canon), symbols=sympy.numbered_symbols('c%d_x' % ci), optimizations='basic')
-        if share_products:
-            repl, red = _share_products(repl, red, 'c%d_x' % ci)
+        repl, red = _class_cse(ci, canon, share_products)
         if memo is not None:
             memo[key] = (repl, red)
         return repl, red
@@ -533,6 +598,9 @@ def emit_rowlane_members(spec, d, meta, make_printer, hoist=True):
          % (meta['max_ys'], meta['max_ps'], meta['max_jy'], meta['max_jp']),
          "  static constexpr int RL_LARGEST_CLASS = %d;  // rows evaluated side by side" %
          max(len(c['rows']) for c in classes),
+         "  // every class body gives f == 0 exactly on all-zero operands (no select for lanes without a row)",
+         "  static constexpr bool RL_F_ZERO_OFF_ROW = %s;" %
+         ('true' if f_zero_off_row(classes, meta.get('share_products', False)) else 'false'),
          "  // table accessors (the tables are namespace-scope __constant__ arrays above)",
          "  __device__ __forceinline__ static int rl_class(int row) { return SBM_RL_CLASS[row]; }",
          "  __device__ __forceinline__ static int rl_ys(int slot, int row) { return SBM_RL_YS[slot * NV + row]; }",
