@@ -107,6 +107,33 @@ struct AssembleLds {
   SBM_ASM_HD size_t bytes() const { return end; }
 };
 
+// The instantiation of k_assemble a launch takes: a pure function of the shape, so that it can be checked on the host
+// (tests/test_assemble_tile_cpu.py).
+//   rows   how many rows of J a thread of pass A keeps in registers between the model Jacobian and its scaling
+//          (SBM_ASSEMBLE_TILE_*), or 0: the Jacobian makes the trip through global memory (pass A stores it, pass B
+//          loads, scales and stores it again).  A thread's rows are r = row lane, + rpp, ...: ceil(R / rpp) of them.
+//          0 for shapes beyond the largest tile and for q > nthr (several passes over the columns).
+//   prog   the project has custom observables (row_w0 present): the postfix interpreter is compiled in
+//   log    the logarithmic loss: log() and the plain-row table are compiled in
+#define SBM_ASSEMBLE_TILE_SMALL 4
+#define SBM_ASSEMBLE_TILE_LARGE 12
+struct AssembleForm {
+  int rows, prog, log;
+};
+SBM_ASM_HD inline AssembleForm assemble_form(int R, int q, int programs, int loss, int nthr) {
+  AssembleForm f;
+  f.prog = programs != 0;
+  f.log = loss == 1;   // SBM_LOSS_LOG_SQUARE (include/sbm.h)
+  f.rows = 0;
+  if (R > 0 && q <= nthr) {
+    const int rpp = nthr / (q > 0 ? q : 1);
+    const int per_thread = (R + rpp - 1) / rpp;
+    if (per_thread <= SBM_ASSEMBLE_TILE_SMALL) f.rows = SBM_ASSEMBLE_TILE_SMALL;
+    else if (per_thread <= SBM_ASSEMBLE_TILE_LARGE) f.rows = SBM_ASSEMBLE_TILE_LARGE;
+  }
+  return f;
+}
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 
@@ -165,9 +192,14 @@ __device__ __forceinline__ void assemble_carve(AssembleBlock& s, const AssembleL
   s.bad = bad;
 }
 
+// The steps are templates over what the instantiation compiles in (AssembleForm): LOG the logarithmic loss (the
+// launcher takes LOG == (a.loss == SBM_LOSS_LOG_SQUARE)), PROG the postfix interpreter of custom observables.
+static_assert(SBM_LOSS_LOG_SQUARE == 1, "assemble_form() spells the logarithmic loss as 1");
+
 // does row r take the logarithmic form of the residual?
+template <bool LOG>
 __device__ __forceinline__ bool assemble_log_row(const AssembleArgs& a, int r) {
-  return a.loss == SBM_LOSS_LOG_SQUARE && !(a.row_plain && a.row_plain[r]);
+  return LOG && !(a.row_plain && a.row_plain[r]);
 }
 
 __device__ __forceinline__ double* assemble_J(const AssembleArgs& a, int v) {
@@ -175,6 +207,7 @@ __device__ __forceinline__ double* assemble_J(const AssembleArgs& a, int v) {
 }
 
 // the row tables into LDS
+template <bool PROG>
 __device__ __forceinline__ void assemble_stage_rows(const AssembleArgs& a, const AssembleBlock& s) {
   const int tid = threadIdx.x;
   if (tid == 0) *s.bad = 0;
@@ -182,7 +215,7 @@ __device__ __forceinline__ void assemble_stage_rows(const AssembleArgs& a, const
     s.d[r] = a.row_data[r];
     s.sg[r] = a.row_sigma[r];
     s.rsf[r] = a.row_sf[r];
-    s.rw0[r] = (a.row_w0 && !a.sims_in) ? a.row_w0[r] : -1;
+    s.rw0[r] = (PROG && a.row_w0 && !a.sims_in) ? a.row_w0[r] : -1;
     if (!a.sims_in) {
       const int e = a.row_exp[r], v0 = a.row_var_off[r];
       s.rexp[r] = e;
@@ -212,6 +245,7 @@ __device__ __forceinline__ void assemble_status_and_steps(const AssembleArgs& a,
 }
 
 // sample + map: sims[r] = sum_{var in vars(r)} Y[traj][tidx][var], or the row's custom observable
+template <bool PROG, bool LOG>
 __device__ __forceinline__ void assemble_sample(const AssembleArgs& a, const AssembleBlock& s) {
   const int tid = threadIdx.x, v = s.v, R = a.R, E = a.E;
   for (int r = tid; r < R; r += blockDim.x) {
@@ -220,21 +254,24 @@ __device__ __forceinline__ void assemble_sample(const AssembleArgs& a, const Ass
       sv = a.sims_in[(size_t)v * R + r];
     } else {
       const double* Yb = a.Y + (size_t)v * E * a.n_t * a.NV + s.roff[r];
-      if (s.rw0[r] >= 0) {
+      if (PROG && s.rw0[r] >= 0) {
         // custom observable: value g(y), and dg/dy_k parked in LDS for the Jacobian pass
         const int32_t* sub = a.prog_sub_off + a.prog_base[a.row_prog[r]];
         const int32_t* vars = a.row_vars + s.rv0[r];
         const double tr = a.row_time[r];
-        sv = sbm_prog_eval(a.prog_code + sub[0], a.prog_const, Yb, vars, tr);
-        if (a.S)
-          for (int k = 0; k < s.rnv[r]; ++k)
-            s.w[s.rw0[r] + k] = sbm_prog_eval(a.prog_code + sub[1 + k], a.prog_const, Yb, vars, tr);
+        // (subprogram 0 is the value, 1 + k is dg/dy_k; one call site: the interpreter is inlined once)
+        const int nsub = a.S ? 1 + s.rnv[r] : 1;
+        for (int k = 0; k < nsub; ++k) {
+          const double val = sbm_prog_eval(a.prog_code + sub[k], a.prog_const, Yb, vars, tr);
+          if (k == 0) sv = val;
+          else s.w[s.rw0[r] + k - 1] = val;
+        }
       } else if (s.rnv[r] == 1) sv = Yb[s.rvar[r]];
       else for (int k = s.rv0[r]; k < s.rv0[r] + s.rnv[r]; ++k) sv += Yb[a.row_vars[k]];
     }
     s.sim[r] = sv;
     // NaN simulations -> inf rows; the log loss cannot take a non-positive simulation either
-    const bool logrow = assemble_log_row(a, r);
+    const bool logrow = assemble_log_row<LOG>(a, r);
     if (!(sv == sv) || (logrow && !(sv > 0.0))) atomicMax(s.bad, (int)SBM_NON_FINITE);
   }
 }
@@ -254,14 +291,21 @@ __device__ __forceinline__ void assemble_fill_failed(const AssembleArgs& a, cons
   if (a.sf_grad) for (int i = tid; i < G * q; i += blockDim.x) a.sf_grad[(size_t)v * G * q + i] = __builtin_nan("");
 }
 
-// scale factors B_g = sum(s d / sigma^2) / sum(s^2 / sigma^2)
+// scale factors B_g = sum(s d / sigma^2) / sum(s^2 / sigma^2).  The 2 G sums are reduced side by side: every
+// wavefront parks its 2 G butterfly results in LDS, one barrier, and the thread of group g adds the wavefront partials
+// of its two sums in wavefront order from +0.0 -- the additions of block_sum, without its two barriers per sum.
+// The partials lie in `part` ([2 G][wavefronts], at most 8 Gn doubles of its 2 Gn rpp q >= 256 Gn), which is zeroed
+// only afterwards.  The caller's barrier publishes B, sde and sds.
+template <bool LOG>
 __device__ __forceinline__ void assemble_scale_factors(const AssembleArgs& a, const AssembleBlock& s) {
   const int tid = threadIdx.x, v = s.v, R = a.R, G = a.G;
+  const int wf = tid >> 6, nwf = blockDim.x >> 6;
+  double* wpart = s.part;
   for (int g = 0; g < G; ++g) {
     double sde = 0.0, sds = 0.0;
     for (int r = tid; r < R; r += blockDim.x) {
       if (s.rsf[r] == g) {
-        if (a.loss == SBM_LOSS_LOG_SQUARE) {
+        if (LOG) {
           // log_scale_factor.py:17-28: weights 1/(sigma/d)^2; log B = sum(w (log d - log s)) / sum(w)
           const double w = (s.d[r] * s.d[r]) / (s.sg[r] * s.sg[r]);
           sde += (log(s.d[r]) - log(s.sim[r])) * w;
@@ -273,19 +317,28 @@ __device__ __forceinline__ void assemble_scale_factors(const AssembleArgs& a, co
         }
       }
     }
-    sde = block_sum(sde, s.red);
-    sds = block_sum(sds, s.red);
-    if (tid == 0) {
-      s.sde[g] = sde;
-      s.sds[g] = sds;
-      const double B = (a.loss == SBM_LOSS_LOG_SQUARE) ? exp(sde / sds) : sde / sds;
-      s.B[g] = B;
-      if (a.sf) a.sf[(size_t)v * G + g] = B;
+    sde = wave_sum(sde);
+    sds = wave_sum(sds);
+    if ((tid & 63) == 0) {
+      wpart[(2 * g + 0) * nwf + wf] = sde;
+      wpart[(2 * g + 1) * nwf + wf] = sds;
     }
+  }
+  __syncthreads();
+  for (int g = tid; g < G; g += blockDim.x) {
+    double sde = 0.0, sds = 0.0;
+    for (int i = 0; i < nwf; ++i) sde += wpart[(2 * g + 0) * nwf + i];
+    for (int i = 0; i < nwf; ++i) sds += wpart[(2 * g + 1) * nwf + i];
+    s.sde[g] = sde;
+    s.sds[g] = sds;
+    const double B = LOG ? exp(sde / sds) : sde / sds;
+    s.B[g] = B;
+    if (a.sf) a.sf[(size_t)v * G + g] = B;
   }
 }
 
 // residuals of the measurement, prior and scale-factor-prior rows, and their sum of squares
+template <bool LOG>
 __device__ __forceinline__ void assemble_residuals(const AssembleArgs& a, const AssembleBlock& s) {
   const int tid = threadIdx.x, v = s.v, R = a.R, q = a.q;
   const int RT = R + a.NPR + a.NSP;
@@ -295,7 +348,7 @@ __device__ __forceinline__ void assemble_residuals(const AssembleArgs& a, const 
     if (r < R) {
       const int g = s.rsf[r];
       const double B = g >= 0 ? s.B[g] : 1.0;
-      const bool logrow = assemble_log_row(a, r);
+      const bool logrow = assemble_log_row<LOG>(a, r);
       res = logrow ? (log(B * s.sim[r]) - log(s.d[r])) / s.sg[r]
                    : (B * s.sim[r] - s.d[r]) / s.sg[r];
       s.res[r] = res;
@@ -327,9 +380,69 @@ __device__ __forceinline__ void assemble_flush_partials(const AssembleBlock& s, 
   s.part[((size_t)(1 * s.Gn + g) * s.rpp + rl) * q + c] += jds;
 }
 
+// What a thread of pass A carries down its rows of one column: the group it is summing for and the two sums
+// (the products J^T (d/sigma^2), J^T (s/sigma^2) of that group over the thread's rows so far).
+struct AssembleRun {
+  int gcur;
+  double jde, jds;
+};
+
+// row r's entry jm of the model Jacobian into the thread's running sums
+template <bool LOG>
+__device__ __forceinline__ void assemble_accumulate(const AssembleBlock& s, AssembleRun& run, int q, int r, int rl, int c,
+                                                    double jm) {
+  const int g = s.rsf[r];
+  if (g != run.gcur) {  // rows of one group are mostly consecutive: flush on change
+    if (run.gcur >= 0) assemble_flush_partials(s, q, run.gcur, rl, c, run.jde, run.jds);
+    run.gcur = g; run.jde = 0.0; run.jds = 0.0;
+  }
+  if (g >= 0) {
+    if (LOG) {  // log_scale_factor.py:30-36: sum J / (s (sigma/d)^2)
+      run.jde += jm * (s.d[r] * s.d[r]) / (s.sg[r] * s.sg[r] * s.sim[r]);
+    } else {
+      const double w = 1.0 / (s.sg[r] * s.sg[r]);
+      run.jde += jm * s.d[r] * w;
+      run.jds += jm * s.sim[r] * w;
+    }
+  }
+}
+
+// The model parameters of experiment e that read project column c: inv_m[k0 .. k1), and the sensitivity column of the
+// only one (the common case), -1 where that parameter has no sensitivity column, -2 where the slot has none or several
+struct AssembleReaders {
+  int k0, k1, sc1;
+};
+__device__ __forceinline__ AssembleReaders assemble_readers(const AssembleArgs& a, int e, int c) {
+  AssembleReaders m;
+  m.k0 = a.inv_ptr[e * (a.q + 1) + c];
+  m.k1 = a.inv_ptr[e * (a.q + 1) + c + 1];
+  m.sc1 = (m.k1 - m.k0 == 1) ? a.sens_col[a.inv_m[m.k0]] : -2;
+  return m;
+}
+
+// sum over the column's readers and the row's variables: every row kind that is not one variable read by one parameter
+template <bool PROG>
+__device__ __forceinline__ double assemble_row_sum(const AssembleArgs& a, const AssembleBlock& s, const double* Sb, int r,
+                                                   int w0, const AssembleReaders& m) {
+  double jm = 0.0;
+  for (int k = m.k0; k < m.k1; ++k) {
+    const int sc = a.sens_col[a.inv_m[k]];
+    if (sc < 0) continue;
+    if (!PROG || w0 < 0) {
+      for (int kk = s.rv0[r]; kk < s.rv0[r] + s.rnv[r]; ++kk) jm += Sb[(size_t)a.row_vars[kk] * a.NK + sc];
+    } else {   // custom observable: sum_k dg/dy_k * S[var_k][sc]
+      for (int kk = 0; kk < s.rnv[r]; ++kk)
+        jm = fma(s.w[w0 + kk], Sb[(size_t)a.row_vars[s.rv0[r] + kk] * a.NK + sc], jm);
+    }
+  }
+  return jm;
+}
+
 // Pass A: model Jacobian with the log-parameter chain rule (base_project.py:450-455,482-485):
 //   Jm[r][c] = exp(theta_c) * sum_{model params m of experiment e reading slot c} sum_{var in vars(r)} S[var][m]
 // written to J / Jmodel; accumulated per SF group: the two products J^T (d/sigma^2), J^T (s/sigma^2)
+// This is the form through global memory (AssembleForm::rows == 0): J holds the model Jacobian until pass B.
+template <bool PROG, bool LOG>
 __device__ __forceinline__ void assemble_model_jacobian(const AssembleArgs& a, const AssembleBlock& s) {
   const int tid = threadIdx.x, v = s.v, R = a.R, q = a.q, E = a.E;
   const int cw = s.cw, rpp = s.rpp;
@@ -341,9 +454,9 @@ __device__ __forceinline__ void assemble_model_jacobian(const AssembleArgs& a, c
     const int c = c0 + cl;
     if (c >= q || rl >= rpp) continue;
     const double dth = a.Jm_in ? 1.0 : exp(th[c]);
-    int gcur = -1;
-    int e_cur = -1, k0 = 0, k1 = 0, sc1 = -1;
-    double jde = 0.0, jds = 0.0;
+    int e_cur = -1;
+    AssembleReaders m = {0, 0, -1};
+    AssembleRun run = {-1, 0.0, 0.0};
     for (int r = rl; r < R; r += rpp) {
       double jm = 0.0;
       if (a.Jm_in) {
@@ -352,50 +465,96 @@ __device__ __forceinline__ void assemble_model_jacobian(const AssembleArgs& a, c
         const int e = s.rexp[r];
         if (e != e_cur) {   // rows are sorted by experiment: the column's model parameters change rarely
           e_cur = e;
-          k0 = a.inv_ptr[e * (q + 1) + c];
-          k1 = a.inv_ptr[e * (q + 1) + c + 1];
-          sc1 = (k1 - k0 == 1) ? a.sens_col[a.inv_m[k0]] : -2;   // the common case: one model parameter per slot
+          m = assemble_readers(a, e, c);
         }
         const double* Sb = a.S + ((size_t)v * E * a.n_t * a.NV + s.roff[r]) * a.NK;
-        const int w0 = s.rw0[r];
-        if (sc1 >= 0 && s.rnv[r] == 1 && w0 < 0) {
-          jm = Sb[(size_t)s.rvar[r] * a.NK + sc1];
-        } else if (sc1 != -1) {
-          for (int k = k0; k < k1; ++k) {
-            const int sc = a.sens_col[a.inv_m[k]];
-            if (sc < 0) continue;
-            if (w0 < 0) {
-              for (int kk = s.rv0[r]; kk < s.rv0[r] + s.rnv[r]; ++kk) jm += Sb[(size_t)a.row_vars[kk] * a.NK + sc];
-            } else {   // custom observable: sum_k dg/dy_k * S[var_k][sc]
-              for (int kk = 0; kk < s.rnv[r]; ++kk)
-                jm = fma(s.w[w0 + kk], Sb[(size_t)a.row_vars[s.rv0[r] + kk] * a.NK + sc], jm);
-            }
-          }
+        const int w0 = PROG ? s.rw0[r] : -1;
+        if (m.sc1 >= 0 && s.rnv[r] == 1 && w0 < 0) {
+          jm = Sb[(size_t)s.rvar[r] * a.NK + m.sc1];   // the common case: one model parameter per slot
+        } else if (m.sc1 != -1) {
+          jm = assemble_row_sum<PROG>(a, s, Sb, r, w0, m);
         }
         jm *= dth;
       }
       if (Jm) Jm[(size_t)r * q + c] = jm;
       if (Jv) Jv[(size_t)r * q + c] = jm;
-      const int g = s.rsf[r];
-      if (g != gcur) {  // rows of one group are mostly consecutive: flush on change
-        if (gcur >= 0) assemble_flush_partials(s, q, gcur, rl, c, jde, jds);
-        gcur = g; jde = 0.0; jds = 0.0;
-      }
-      if (g >= 0) {
-        if (a.loss == SBM_LOSS_LOG_SQUARE) {  // log_scale_factor.py:30-36: sum J / (s (sigma/d)^2)
-          jde += jm * (s.d[r] * s.d[r]) / (s.sg[r] * s.sg[r] * s.sim[r]);
-        } else {
-          const double w = 1.0 / (s.sg[r] * s.sg[r]);
-          jde += jm * s.d[r] * w;
-          jds += jm * s.sim[r] * w;
-        }
-      }
+      assemble_accumulate<LOG>(s, run, q, r, rl, c, jm);
     }
-    if (gcur >= 0) assemble_flush_partials(s, q, gcur, rl, c, jde, jds);
+    if (run.gcur >= 0) assemble_flush_partials(s, q, run.gcur, rl, c, run.jde, run.jds);
   }
 }
 
+// Pass A with the thread's K rows of the model Jacobian kept in registers (AssembleForm::rows == K; q <= blockDim.x:
+// one pass over the columns, a thread is (row lane rl, column c) and owns rows rl, rl + rpp, ... < R, at most K).
+// The loads of all K rows are issued before the first is used: a row that is not there or not of the common kind
+// loads the vector's first entry instead, so that no load hangs on a branch.  The sums then run over the rows in
+// the order of the form above.  J is not touched; Jmodel is stored here.
+template <int K, bool PROG, bool LOG>
+__device__ __forceinline__ void assemble_model_jacobian_tile(const AssembleArgs& a, const AssembleBlock& s, double (&jm)[K]) {
+  const int tid = threadIdx.x, v = s.v, R = a.R, q = a.q;
+  const int rpp = s.rpp;
+  const int c = tid % s.cw, rl = tid / s.cw;
+#pragma unroll
+  for (int k = 0; k < K; ++k) jm[k] = 0.0;
+  if (rl >= rpp) return;
+  double* Jm = a.Jmodel ? a.Jmodel + (size_t)v * R * q : nullptr;
+  if (a.Jm_in) {
+    const double* Jin = a.Jm_in + (size_t)v * R * q + c;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int r = rl + k * rpp;
+      jm[k] = Jin[(size_t)(r < R ? r : 0) * q];
+    }
+  } else {
+    const double dth = exp(a.Theta[(size_t)v * q + c]);
+    const double* Sv = a.S + (size_t)v * a.E * a.n_t * a.NV * a.NK;
+    int e_cur = -1;
+    AssembleReaders m = {0, 0, -1};
+    unsigned other = 0;     // bit k: row k is there and takes assemble_row_sum (or is exactly zero: sc1 == -1)
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int r = rl + k * rpp;
+      const double* p = Sv;
+      if (r < R) {
+        const int e = s.rexp[r];
+        if (e != e_cur) {
+          e_cur = e;
+          m = assemble_readers(a, e, c);
+        }
+        const int w0 = PROG ? s.rw0[r] : -1;
+        if (m.sc1 >= 0 && s.rnv[r] == 1 && w0 < 0) p = Sv + ((size_t)s.roff[r] + s.rvar[r]) * a.NK + m.sc1;
+        else other |= 1u << k;
+      }
+      jm[k] = *p;
+    }
+    if (other) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        if (other >> k & 1) {
+          const int r = rl + k * rpp;
+          const AssembleReaders mr = assemble_readers(a, s.rexp[r], c);
+          jm[k] = 0.0;
+          if (mr.sc1 != -1) jm[k] = assemble_row_sum<PROG>(a, s, Sv + (size_t)s.roff[r] * a.NK, r, PROG ? s.rw0[r] : -1, mr);
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) jm[k] *= dth;
+  }
+  AssembleRun run = {-1, 0.0, 0.0};
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int r = rl + k * rpp;
+    if (r < R) {
+      if (Jm) Jm[(size_t)r * q + c] = jm[k];
+      assemble_accumulate<LOG>(s, run, q, r, rl, c, jm[k]);
+    }
+  }
+  if (run.gcur >= 0) assemble_flush_partials(s, q, run.gcur, rl, c, run.jde, run.jds);
+}
+
 // dB_g/dtheta_c = jde/sds - 2 sde jds / sds^2   (linear_scale_factor.py:33-42)
+template <bool LOG>
 __device__ __forceinline__ void assemble_sf_gradient(const AssembleArgs& a, const AssembleBlock& s) {
   const int v = s.v, G = a.G, q = a.q, Gn = s.Gn, rpp = s.rpp;
   const int nthr = blockDim.x;
@@ -408,14 +567,45 @@ __device__ __forceinline__ void assemble_sf_gradient(const AssembleArgs& a, cons
     }
     const double sds = s.sds[g], sde = s.sde[g];
     // square: dB = jde/sds - 2 sde jds/sds^2 ; log: dB = B * (-1/W) sum J/(s sigma'^2)
-    const double db = (a.loss == SBM_LOSS_LOG_SQUARE) ? -s.B[g] * jde / sds
-                                                      : jde / sds - 2.0 * sde * jds / (sds * sds);
+    const double db = LOG ? -s.B[g] * jde / sds : jde / sds - 2.0 * sde * jds / (sds * sds);
     s.dB[i] = db;
     if (a.sf_grad) a.sf_grad[(size_t)v * G * q + i] = db;
   }
 }
 
-// Pass B: J = B*Jm + sim (x) dB ; reference_compat: not divided by sigma, prior rows zero
+// Pass B, a measurement row: J = B*Jm + sim (x) dB ; reference_compat: not divided by sigma
+template <bool LOG>
+__device__ __forceinline__ double assemble_scaled_entry(const AssembleArgs& a, const AssembleBlock& s, int r, int c, double val) {
+  const int g = s.rsf[r], q = a.q;
+  if (assemble_log_row<LOG>(a, r)) {
+    // log_squared_loss_function.py:66-98: J/s (+ (dB/dtheta)/B for rows with a scale factor)
+    val = val / s.sim[r];
+    if (g >= 0) val += s.dB[g * q + c] / s.B[g];
+  } else if (g >= 0) {
+    val = s.B[g] * val + s.sim[r] * s.dB[g * q + c];
+  }
+  if (!a.compat) val /= s.sg[r];
+  return val;
+}
+
+// Pass B, a prior row (r >= R); reference_compat: prior rows zero
+__device__ __forceinline__ double assemble_prior_entry(const AssembleArgs& a, const AssembleBlock& s, int r, int c) {
+  const int R = a.R, q = a.q;
+  double val;
+  if (r < R + a.NPR) {
+    const int k = r - R;
+    val = (!a.compat && a.prior_idx[k] == c) ? 1.0 / a.prior_sigma[k] : 0.0;
+  } else {
+    const int k = r - R - a.NPR;  // (dB/dtheta)/B, linear_scale_factor.py:44-53
+    const int g = a.sfp_group[k];
+    val = s.dB[g * q + c] / s.B[g];
+    if (!a.compat) val /= a.sfp_sigma[k];
+  }
+  return val;
+}
+
+// Pass B through global memory: every entry of the model Jacobian pass A left in J, loaded, scaled and stored again
+template <bool LOG>
 __device__ __forceinline__ void assemble_scale_jacobian(const AssembleArgs& a, const AssembleBlock& s) {
   const int R = a.R, q = a.q;
   const int RT = R + a.NPR + a.NSP;
@@ -423,28 +613,28 @@ __device__ __forceinline__ void assemble_scale_jacobian(const AssembleArgs& a, c
   if (!Jv) return;
   for (size_t i = threadIdx.x; i < (size_t)RT * q; i += blockDim.x) {
     const int r = (int)(i / q), c = (int)(i - (size_t)r * q);
-    double val;
-    if (r < R) {
-      const int g = s.rsf[r];
-      val = Jv[i];
-      if (assemble_log_row(a, r)) {
-        // log_squared_loss_function.py:66-98: J/s (+ (dB/dtheta)/B for rows with a scale factor)
-        val = val / s.sim[r];
-        if (g >= 0) val += s.dB[g * q + c] / s.B[g];
-      } else if (g >= 0) {
-        val = s.B[g] * val + s.sim[r] * s.dB[g * q + c];
-      }
-      if (!a.compat) val /= s.sg[r];
-    } else if (r < R + a.NPR) {
-      const int k = r - R;
-      val = (!a.compat && a.prior_idx[k] == c) ? 1.0 / a.prior_sigma[k] : 0.0;
-    } else {
-      const int k = r - R - a.NPR;  // (dB/dtheta)/B, linear_scale_factor.py:44-53
-      const int g = a.sfp_group[k];
-      val = s.dB[g * q + c] / s.B[g];
-      if (!a.compat) val /= a.sfp_sigma[k];
+    Jv[i] = r < R ? assemble_scaled_entry<LOG>(a, s, r, c, Jv[i]) : assemble_prior_entry(a, s, r, c);
+  }
+}
+
+// Pass B on the rows pass A kept: J is stored once.  The prior rows keep the flat loop.
+template <int K, bool LOG>
+__device__ __forceinline__ void assemble_scale_jacobian_tile(const AssembleArgs& a, const AssembleBlock& s, const double (&jm)[K]) {
+  const int R = a.R, q = a.q;
+  const int RT = R + a.NPR + a.NSP;
+  double* Jv = assemble_J(a, s.v);
+  if (!Jv) return;
+  const int c = threadIdx.x % s.cw, rl = threadIdx.x / s.cw;
+  if (rl < s.rpp) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int r = rl + k * s.rpp;
+      if (r < R) Jv[(size_t)r * q + c] = assemble_scaled_entry<LOG>(a, s, r, c, jm[k]);
     }
-    Jv[i] = val;
+  }
+  for (size_t i = (size_t)R * q + threadIdx.x; i < (size_t)RT * q; i += blockDim.x) {
+    const int r = (int)(i / q), c2 = (int)(i - (size_t)r * q);
+    Jv[i] = assemble_prior_entry(a, s, r, c2);
   }
 }
 
@@ -465,6 +655,8 @@ __device__ __forceinline__ void assemble_gradient(const AssembleArgs& a, const A
   }
 }
 
+// K, PROG, LOG: the AssembleForm of the launch (assemble_form; launch_assemble picks the instantiation)
+template <int K, bool PROG, bool LOG>
 __global__ void __launch_bounds__(256) k_assemble(AssembleArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   __shared__ int s_bad;
@@ -472,10 +664,10 @@ __global__ void __launch_bounds__(256) k_assemble(AssembleArgs a) {
   assemble_carve(s, AssembleLds(a.R, a.G, a.q, a.NW, blockDim.x), (char*)smem, &s_bad, blockIdx.x);
   const int v = s.v, tid = threadIdx.x, R = a.R;
 
-  assemble_stage_rows(a, s);
+  assemble_stage_rows<PROG>(a, s);
   __syncthreads();
   assemble_status_and_steps(a, s);
-  assemble_sample(a, s);
+  assemble_sample<PROG, LOG>(a, s);
   __syncthreads();
   const int bad = s_bad;
   if (a.status && tid == 0) a.status[v] = bad;
@@ -485,18 +677,27 @@ __global__ void __launch_bounds__(256) k_assemble(AssembleArgs a) {
   }
   if (a.sims) for (int r = tid; r < R; r += blockDim.x) a.sims[(size_t)v * R + r] = s.sim[r];
 
-  assemble_scale_factors(a, s);
+  assemble_scale_factors<LOG>(a, s);
   __syncthreads();
-  assemble_residuals(a, s);
+  assemble_residuals<LOG>(a, s);
   if (!a.J && !a.Jmodel && !a.grad && !a.sf_grad) return;
 
   assemble_zero_partials(a, s);
   __syncthreads();
-  assemble_model_jacobian(a, s);      // pass A
-  __syncthreads();
-  assemble_sf_gradient(a, s);
-  __syncthreads();
-  assemble_scale_jacobian(a, s);      // pass B
+  if constexpr (K > 0) {
+    double jm[K];
+    assemble_model_jacobian_tile<K, PROG, LOG>(a, s, jm);      // pass A
+    __syncthreads();
+    assemble_sf_gradient<LOG>(a, s);
+    __syncthreads();
+    assemble_scale_jacobian_tile<K, LOG>(a, s, jm);            // pass B
+  } else {
+    assemble_model_jacobian<PROG, LOG>(a, s);                  // pass A
+    __syncthreads();
+    assemble_sf_gradient<LOG>(a, s);
+    __syncthreads();
+    assemble_scale_jacobian<LOG>(a, s);                        // pass B
+  }
   if (a.grad) {
     __syncthreads();
     assemble_gradient(a, s);

@@ -619,17 +619,41 @@ static int launch_lds(sbm_ctx* ctx, void (*kernel)(P...), dim3 grid, dim3 block,
 // The dynamic block of k_assemble (AssembleLds) and the kernel's static LDS (s_bad, padded to the dynamic block's
 // alignment: 16 bytes, read from the code object) have to fit the device's workgroup limit TOGETHER: compared alone with
 // a literal 160 KB, a dynamic block within 16 bytes of the limit was accepted here and refused by the runtime at the launch.
+//
+// The instantiation is assemble_form's (sbm_assemble.hpp).  Developer switch, read at every launch:
+// SBM_ASSEMBLE_ROWS_IN_REGS=0 takes the form through global memory (rows == 0) for every shape -- the reference the
+// register-tile forms are compared with bit for bit (tests/test_gpu_assemble_one_trip.py), and the A/B timing.
+// Under SBM_DEBUG_LAUNCH the launcher names the instantiation.
+template <int K, bool PROG>
+static int launch_assemble_as(sbm_ctx* ctx, const AssembleArgs& g, int V, size_t lds, bool log) {
+  if (log) return launch_lds(ctx, k_assemble<K, PROG, true>, dim3(V), dim3(256), lds, g);
+  return launch_lds(ctx, k_assemble<K, PROG, false>, dim3(V), dim3(256), lds, g);
+}
+template <int K>
+static int launch_assemble_as(sbm_ctx* ctx, const AssembleArgs& g, int V, size_t lds, bool prog, bool log) {
+  return prog ? launch_assemble_as<K, true>(ctx, g, V, lds, log) : launch_assemble_as<K, false>(ctx, g, V, lds, log);
+}
+
 static int launch_assemble(sbm_ctx* ctx, const AssembleArgs& g, int V, const char* who) {
   const size_t lds = AssembleLds(g.R, g.G, g.q, g.NW, 256).bytes();
-  static const size_t stat = [] {   // asked once: the kernel is the same on every device
+  static const size_t stat = [] {   // asked once: the same on every device and in every instantiation (s_bad)
     hipFuncAttributes fa;
-    return hipFuncGetAttributes(&fa, (const void*)k_assemble) == hipSuccess ? (size_t)fa.sharedSizeBytes : (size_t)16;
+    return hipFuncGetAttributes(&fa, (const void*)k_assemble<0, false, false>) == hipSuccess ? (size_t)fa.sharedSizeBytes : (size_t)16;
   }();
   const size_t limit = (size_t)lm_lds_limit(ctx);
   if (lds + stat > limit)
     return sbm_fail(SBM_E_ARG, "%s: project too large for the assembly kernel (%zu B of LDS + %zu B static, the workgroup's limit is %zu B)",
                     who, lds, stat, limit);
-  return launch_lds(ctx, k_assemble, dim3(V), dim3(256), lds, g);
+  AssembleForm f = assemble_form(g.R, g.q, g.row_w0 != nullptr && !g.sims_in, g.loss, 256);
+  const char* in_regs = getenv("SBM_ASSEMBLE_ROWS_IN_REGS");
+  if (in_regs && in_regs[0] == '0' && !in_regs[1]) f.rows = 0;
+  if (getenv("SBM_DEBUG_LAUNCH"))
+    fprintf(stderr, "k_assemble<%d, %d, %d>: R %d q %d G %d, %d vectors, %zu B of LDS\n", f.rows, f.prog, f.log, g.R, g.q, g.G, V, lds);
+  switch (f.rows) {
+    case SBM_ASSEMBLE_TILE_LARGE: return launch_assemble_as<SBM_ASSEMBLE_TILE_LARGE>(ctx, g, V, lds, f.prog, f.log);
+    case SBM_ASSEMBLE_TILE_SMALL: return launch_assemble_as<SBM_ASSEMBLE_TILE_SMALL>(ctx, g, V, lds, f.prog, f.log);
+    default: return launch_assemble_as<0>(ctx, g, V, lds, f.prog, f.log);
+  }
 }
 
 // the static part of the kernel's arguments: the project's tables
