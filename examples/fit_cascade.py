@@ -19,7 +19,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sysbio_modeling_amd import models_zoo
 from sysbio_modeling_amd.model import OdeModel
-from sysbio_modeling_amd.project.ensembles import ensemble_log_params_batch, ensemble_predictions
+from sysbio_modeling_amd.project.ensembles import ensemble_diagnostics, ensemble_log_params_batch, ensemble_predictions
 from sysbio_modeling_amd.symbolic import zoo_model
 
 
@@ -49,6 +49,10 @@ def main():
         t0 = time.time()
         ens, ens_F, ratio = ensemble_log_params_batch(proj, start, steps=200, sampler=sampler, **chains)
         print("MCMC (%s sampler): 64 chains x 200 steps in %.2f s, acceptance %.2f" % (sampler, time.time() - t0, ratio.mean()))
+    # has it converged, and how many independent samples does it hold?  (200 steps from one start: it has not)
+    diag = ensemble_diagnostics(ens, ens_F)
+    print("    diagnostics of the 64 chains: max r_hat %.2f, min ess %.0f of %d kept steps x 64, %d of %d series with a truncated "
+          "window" % (np.nanmax(diag['r_hat']), np.nanmin(diag['ess']), ens.shape[0], int(diag['truncated'].sum()), diag['tau'].size))
     ensemble_log_params_batch(proj, start, steps=2, sampler='device_recalc', **chains)
     t0 = time.time()
     _, _, ratio_r = ensemble_log_params_batch(proj, start, steps=200, sampler='device_recalc', **chains)

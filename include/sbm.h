@@ -658,6 +658,37 @@ int sbm_ensemble_stats(sbm_ctx* ctx, const double* values_dev, const int32_t* st
                        const double* levels, int32_t Q, double* mean_dev, double* sd_dev, double* quant_dev,
                        int32_t* used_dev, int32_t* n_used_dev);
 
+/* ---- sampler convergence diagnostics: autocorrelation, tau, ESS, split-R-hat ---- */
+/* replaces autocorrelation() (project/Ensembles.py:14-29) for S series at once, on the record as the device samplers write
+ * it, and adds what is derived from it.
+ * values   [N][.]   device; step i of series s at values[i * step_stride + s], s < S.  step_stride = S for a dense record,
+ *                   thin * S reads every thin-th step of it.  For an ensemble (n_kept, C, q): S = C q, s = c q + j.
+ * ac       [S][K]   device out, series-major: ac[s][k] = (r_k / (N - k)) / (r_0 / N), r_k = sum_{i < N-k} d_i d_{i+k},
+ *                   d = x - mean(x): de-meaned, zero-padded, every lag divided by the number of its terms and by lag 0,
+ *                   the reference's normalisation.  ac[s][0] == 1.
+ * tau      [S]      device out, nullable: Geyer's initial positive sequence, Gamma_m = ac[2m] + ac[2m+1], M the first m
+ *                   with Gamma_m <= 0, tau = -1 + 2 sum_{m < M} Gamma_m; an odd trailing lag is ignored.  No such m among
+ *                   the K / 2 complete pairs: the sum over all of them, a lower bound, and flag bit 1.
+ * moments  [S][4]   device out, nullable: mean and unbiased variance of the first n = N / 2 steps, then of the last n (an
+ *                   odd N leaves the middle step out of both)
+ * flags    [S]      device out, nullable: bit 0 = constant series (min == max: ac and tau are NaN, the variances 0),
+ *                   bit 1 = tau truncated (set only where tau is asked for)
+ * A series is kept in the LDS of one workgroup: N <= SBM_CHAIN_MAX_STEPS, more is SBM_E_ARG (no host fallback).
+ * 2 <= N, 1 <= K <= N, step_stride >= S; S == 0 launches nothing.  Every sum has a fixed shape: the same input gives the
+ * same bits.  Asynchronous on the context's stream.  An added export: SBM_ABI_VERSION is unchanged. */
+#define SBM_CHAIN_MAX_STEPS 16384
+int sbm_chain_autocorr(sbm_ctx* ctx, const double* values_dev, int32_t N, int64_t S, int64_t step_stride, int32_t K,
+                       double* ac_dev, double* tau_dev, double* moments_dev, int32_t* flags_dev);
+
+/* per parameter j, from the moments and tau of the C q series s = c q + j of an N-step record:
+ * rhat [q]  split-R-hat over the 2C half-chains of length n = N / 2: W = mean of their variances, B / n = unbiased variance
+ *           of their means, sqrt(((n - 1) / n W + B / n) / W); W == 0 gives NaN
+ * ess  [q]  sum_c N / tau[c][j], chains with NaN tau left out (all left out: NaN).  The sum treats the chains as samples of
+ *           one distribution: it means something only where rhat is close to 1.
+ * C >= 1, q >= 1, N >= 2.  Asynchronous on the context's stream. */
+int sbm_chain_summary(sbm_ctx* ctx, const double* moments_dev, const double* tau_dev, int32_t N, int32_t C, int32_t q,
+                      double* rhat_dev, double* ess_dev);
+
 /* ---- multi-GPU: the one exchange of the path ----------------------------- */
 /* The path shards by parameter vector with no data-path collective; what every
  * rank may want afterwards is everybody's per-vector ||r||^2 (sbm_residuals_batch's

@@ -25,6 +25,7 @@ SBM_IMPLICIT_EXTRAP = 6
 IMPLICIT_MAX_NV = 128     # include/sbm.h: SBM_IMPLICIT_MAX_NV
 ENSEMBLE_MAX_MEMBERS = 16384     # include/sbm.h: SBM_ENSEMBLE_MAX_MEMBERS
 SAMPLING_AXES_MAX_Q = 96         # include/sbm.h: SBM_SAMPLING_AXES_MAX_Q
+CHAIN_MAX_STEPS = 16384          # include/sbm.h: SBM_CHAIN_MAX_STEPS
 ENSEMBLE_MAX_LEVELS = 64         # quantile levels per sbm_ensemble_stats call
 STATUS_NAMES = {0: 'ok', 1: 'max_steps', 2: 'non_finite', 3: 'step_underflow', 4: 'newton_fail',
                 5: 'tolerance_not_reached'}
@@ -118,6 +119,8 @@ SIGNATURES = {
                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sbm_project_trajectory_steps': (ctypes.c_int, [_vp, _i32, _vp]),
     'sbm_ensemble_stats': (ctypes.c_int, [_vp, _vp, _vp, _i32, ctypes.c_int64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'sbm_chain_autocorr': (ctypes.c_int, [_vp, _vp, _i32, ctypes.c_int64, ctypes.c_int64, _i32, _vp, _vp, _vp, _vp]),
+    'sbm_chain_summary': (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     'sbm_loss_eval_host': (ctypes.c_int, [_vp, ctypes.POINTER(LossDesc), _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 

@@ -19,6 +19,8 @@
 //                           recipe; project/Ensembles.py:153-157)
 //   sbm_ensemble_stats.hpp  k_ens_*: statistics over the member axis of an ensemble of trajectories
 //                           (project/Ensembles.py:277-308, 335-361)
+//   sbm_chain_diagnostics.hpp  k_chain_*: autocorrelation, integrated autocorrelation time, effective sample size and
+//                           split-R-hat of the samplers' record (project/Ensembles.py:14-29)
 //   sbm_block_reduce.hpp    the wavefront / workgroup reductions that k_assemble, the fitting and the sampler kernels share
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -33,6 +35,7 @@
 #include "sbm_plugin.h"
 #include "sbm_assemble.hpp"
 #include "sbm_block_reduce.hpp"
+#include "sbm_chain_diagnostics.hpp"
 #include "sbm_ensemble_stats.hpp"
 #include "sbm_lm.hpp"
 #include "sbm_project_check.hpp"
@@ -1145,6 +1148,67 @@ extern "C" int sbm_ensemble_stats(sbm_ctx* ctx, const double* values, const int3
                       : launch_lds(ctx, k_ens_columns<256>, dim3(blocks), dim3(256), lds, a, lv))
       return rc;
   }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Chain diagnostics: autocorrelation, tau, half-chain moments; split-R-hat and ESS (kernels, the work split and the LDS
+// layout: sbm_chain_diagnostics.hpp).
+// ---------------------------------------------------------------------------------------------
+extern "C" int sbm_chain_autocorr(sbm_ctx* ctx, const double* values, int32_t N, int64_t S, int64_t step_stride, int32_t K,
+                                  double* ac, double* tau, double* moments, int32_t* flags) {
+  if (!ctx || ((!values || !ac) && S > 0)) return sbm_fail(SBM_E_ARG, "sbm_chain_autocorr: NULL argument");
+  if (S < 0) return sbm_fail(SBM_E_ARG, "sbm_chain_autocorr: bad sizes S=%lld", (long long)S);
+  if (N < 2) return sbm_fail(SBM_E_ARG, "sbm_chain_autocorr: %d steps; a series needs N >= 2", N);
+  if (N > SBM_CHAIN_MAX_STEPS)
+    return sbm_fail(SBM_E_ARG, "sbm_chain_autocorr: %d steps; a series is kept in the LDS of one workgroup, which holds "
+                    "SBM_CHAIN_MAX_STEPS = %d (thin the record with step_stride)", N, SBM_CHAIN_MAX_STEPS);
+  if (K < 1 || K > N) return sbm_fail(SBM_E_ARG, "sbm_chain_autocorr: %d lags of %d steps (1 <= K <= N)", K, N);
+  if (step_stride < S)
+    return sbm_fail(SBM_E_ARG, "sbm_chain_autocorr: step_stride %lld < S = %lld", (long long)step_stride, (long long)S);
+  if (S == 0) return 0;
+  const bool wide = N >= SBM_CHAIN_WIDE_FROM;
+  int G = 1;
+  if (!wide) {
+    while (2 * G <= SBM_CHAIN_PACK_SLOTS / N && 2 * G <= SBM_CHAIN_PACK_MAX) G *= 2;
+  }
+  const int threads = wide ? 1024 : 256;
+  sbm_chain_args a;
+  a.step_stride = step_stride;
+  a.N = N;
+  a.K = K;
+  a.G = G;
+  a.ld = wide ? N + SBM_CHAIN_PAD : ((N + SBM_CHAIN_PAD) | 1);
+  const size_t lds = sizeof(double) * sbm_chain_lds_doubles(threads, G, a.ld);
+  const int64_t chunk = (int64_t)G * 0x4000000ll;      // series of one launch: the grid's x extent, n_series in 32 bits
+  for (int64_t s0 = 0; s0 < S; s0 += chunk) {
+    const int64_t ns = S - s0 < chunk ? S - s0 : chunk;
+    a.values = values + s0;
+    a.n_series = (int32_t)ns;
+    a.ac = ac + (size_t)s0 * (size_t)K;
+    a.moments = moments ? moments + (size_t)s0 * 4 : nullptr;
+    a.flags = flags ? flags + s0 : nullptr;
+    const unsigned blocks = (unsigned)((ns + G - 1) / G);
+    if (int rc = wide ? launch_lds(ctx, k_chain_autocorr<1024>, dim3(blocks), dim3(1024), lds, a)
+                      : launch_lds(ctx, k_chain_autocorr<256>, dim3(blocks), dim3(256), lds, a))
+      return rc;
+    if (tau) {
+      hipLaunchKernelGGL(k_chain_tau, dim3((unsigned)((ns + 3) / 4)), dim3(256), 0, ctx->stream, (const double*)a.ac, a.n_series, K,
+                         tau + s0, a.flags);
+      SBM_HIP(hipGetLastError());
+    }
+  }
+  return 0;
+}
+
+extern "C" int sbm_chain_summary(sbm_ctx* ctx, const double* moments, const double* tau, int32_t N, int32_t C, int32_t q,
+                                 double* rhat, double* ess) {
+  if (!ctx || !moments || !tau || !rhat || !ess) return sbm_fail(SBM_E_ARG, "sbm_chain_summary: NULL argument");
+  if (N < 2) return sbm_fail(SBM_E_ARG, "sbm_chain_summary: %d steps; a series needs N >= 2", N);
+  if (C < 1 || q < 1) return sbm_fail(SBM_E_ARG, "sbm_chain_summary: bad sizes C=%d q=%d", C, q);
+  SBM_HIP(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(k_chain_summary, dim3((unsigned)((q + 3) / 4)), dim3(256), 0, ctx->stream, moments, tau, N, C, q, rhat, ess);
+  SBM_HIP(hipGetLastError());
   return 0;
 }
 
