@@ -3,7 +3,7 @@
 The reference has no implicit integrator of its own: stiff systems go to LSODA, which switches to
 BDF by itself (model/ode_model.py:122-123,167-168, optional analytic Jacobian ``Dfun`` :114-120).
 BASELINE configs[4] asks for an implicit-midpoint GPU integrator; this module restates THAT scheme
-on the CPU in dense numpy, step for step as csrc/sbm_integrators.hpp::sbm_imid_kernel runs it, so
+on the CPU in dense numpy, step for step as csrc/sbm_implicit_midpoint.hpp::sbm_imid_kernel runs it, so
 the kernel can be checked at the level of the algorithm (tests/test_gpu_implicit.py), while parity
 with the reference's results is checked against ``odeint_oracle`` (LSODA) after extrapolation.
 

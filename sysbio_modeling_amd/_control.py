@@ -4,7 +4,7 @@ midpoint rule, and the stiff fallback of ``method='auto'``.
 The reference never chooses an integrator: ``scipy.integrate.odeint`` is LSODA, which switches between
 Adams and BDF formulas by itself and controls its local error (model/ode_model.py:122-123,167-168), so a
 stiff model "just works" there.  The device integrators are an explicit adaptive pair (DOPRI45) and a
-fixed-step implicit one (implicit midpoint, csrc/sbm_integrators.hpp).  Two loops close the gap:
+fixed-step implicit one (implicit midpoint, csrc/sbm_implicit_midpoint.hpp).  Two loops close the gap:
 
 ``controlled_romberg``   The implicit midpoint rule is run with n, 2n, 4n, ... steps (every step halved
     exactly: ``step_mult``) and the runs are combined in a Romberg table (the symmetric rule's global error

@@ -1,6 +1,6 @@
 // sbm_block_reduce.hpp -- the reductions of the library's own kernels (sbm_core.hip and the headers it includes): a
 // butterfly over the 64 lanes of a wavefront, a sum over a workgroup, and the "neither infinite nor NaN" test.
-// Not for the model plugins: their sbm_wave_sum / sbm_wave_max (sbm_integrators.hpp) broadcast through DPP.
+// Not for the model plugins: their sbm_wave_sum / sbm_wave_max (sbm_wave.hpp) broadcast through DPP.
 #ifndef SBM_BLOCK_REDUCE_HPP
 #define SBM_BLOCK_REDUCE_HPP
 

@@ -1,7 +1,7 @@
 // sbm_implicit_adaptive.hpp -- implicit midpoint with error control INSIDE the kernel (SBM_IMPLICIT_ADAPTIVE).
 //
 // The reference never picks an integrator: scipy.integrate.odeint is LSODA, which goes implicit on a stiff system by
-// itself and controls its error (model/ode_model.py:122-123,167-168).  The fixed-step kernel of sbm_integrators.hpp
+// itself and controls its error (model/ode_model.py:122-123,167-168).  The fixed-step kernel of sbm_implicit_midpoint.hpp
 // (sbm_imid_kernel) needed a host loop around it for that (whole-ensemble runs with n, 2n, 4n, ... steps combined in a
 // Romberg table: _control.py -- seconds per ensemble).  Here the control sits inside the kernel, one launch:
 //

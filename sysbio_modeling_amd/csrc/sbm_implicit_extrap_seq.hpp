@@ -293,6 +293,8 @@ __global__ void __launch_bounds__(64) sbm_iex_seq_kernel(sbm_kernel_args a, doub
                 double ys[M::RL_MAXYS];
 #pragma unroll
                 for (int q = 0; q < M::RL_MAXYS; ++q) ys[q] = sh.YG[grp][yidxA[r][q]];
+                // Own copy of sbm_row_eval (sbm_row_operands.hpp): with the shared one sbm_iex_seq_kernel of stiff16 / stiff24 /
+                // stiff50 is scheduled differently (2957 / 3636, 3009 / 6738, 5084 instructions and all metadata unchanged).
                 double f = 0.0, jy[M::RL_MAXJY], jp[M::RL_MAXJP];
 #pragma unroll
                 for (int q = 0; q < M::RL_MAXJY; ++q) jy[q] = 0.0;

@@ -80,10 +80,9 @@ struct SbmImplicitStepper {
   Sh* sh;
   int lane, chunk;
   bool has_row[RPL];
-  int cls[RPL];
-  int yidx[RPL][M::RL_MAXYS], jyout[RPL][M::RL_MAXJY], apos[RPL][M::RL_MAXJP], mfpos[RPL][M::RL_MAXJY];
+  SbmRowTable<M, RPL> rows;                        // class, operand indices, parameters of this lane's rows
+  int jyout[RPL][M::RL_MAXJY], apos[RPL][M::RL_MAXJP], mfpos[RPL][M::RL_MAXJY];
   int rdpos[RPL], diagslot[RPL];
-  double ps[RPL][M::RL_MAXPS];
 #ifdef SBM_IMPLICIT_REDUNDANT_LU                   // developer A/B switch: the redundant form where the distributed one applies
   static constexpr bool DIST = false;
 #else
@@ -112,11 +111,7 @@ struct SbmImplicitStepper {
       const bool hr = lane + 64 * r < NV;
       const int row = hr ? lane + 64 * r : 0;
       has_row[r] = hr;
-      cls[r] = hr ? M::rl_class(row) : -1;
-#pragma unroll
-      for (int s = 0; s < M::RL_MAXYS; ++s) yidx[r][s] = M::rl_ys(s, row);
-#pragma unroll
-      for (int s = 0; s < M::RL_MAXPS; ++s) ps[r][s] = P[M::rl_ps(s, row)];
+      SBM_ROW_TABLE_LOAD(M, rows, r, P, row, hr, 0)
 #pragma unroll
       for (int s = 0; s < M::RL_MAXJY; ++s) jyout[r][s] = hr ? M::rl_jyout(s, row) : M::NJY + 1;
 #pragma unroll
@@ -222,13 +217,15 @@ struct SbmImplicitStepper {
     for (int r = 0; r < RPL; ++r) {
       double ys[M::RL_MAXYS];
 #pragma unroll
-      for (int q = 0; q < M::RL_MAXYS; ++q) ys[q] = sh->Y[yidx[r][q]];
+      for (int q = 0; q < M::RL_MAXYS; ++q) ys[q] = sh->Y[rows.yidx[r][q]];
+      // Own exchange and own copy of sbm_row_eval: with the shared ones sbm_imid / sbm_imid_adaptive / sbm_iex_kernel are
+      // scheduled differently (the exchange: michaelis_menten vgpr_count 70 -> 71 / 140 -> 141; the evaluation: dense20).
       double f = 0.0, jy[M::RL_MAXJY], jp[M::RL_MAXJP];
 #pragma unroll
       for (int q = 0; q < M::RL_MAXJY; ++q) jy[q] = 0.0;
 #pragma unroll
       for (int q = 0; q < M::RL_MAXJP; ++q) jp[q] = 0.0;
-      M::class_dispatch(cls[r], tm, ys, ps[r], f, jy, jp);
+      M::class_dispatch(rows.cls[r], tm, ys, rows.ps[r], f, jy, jp);
       SBM_LDS_FENCE();
 #pragma unroll
       for (int q = 0; q < M::RL_MAXJP; ++q) sh->A[apos[r][q]] = jp[q];

@@ -56,32 +56,20 @@ struct MfmaSystem {
   // element e = (rt * CT + ct) * 4 + r
   __device__ __forceinline__ static constexpr int col_of(int, int e) { return (e / 4) % CT; }
   Sh* sh;
-  int lane, cbase, cls;
-  int yidx[M::RL_MAXYS], jdpos[M::RL_MAXJY], apos[M::RL_MAXJP];
-  double ps[M::RL_MAXPS];
+  int lane, cbase;
+  SbmRowTable<M, 1> rows;
+  int jdpos[M::RL_MAXJY], apos[M::RL_MAXJP];
 
-  struct Pending { double ys[M::RL_MAXYS]; };
+  using Pending = typename SbmRowTable<M, 1>::Operands;
   struct Token { double f; };
 
   __device__ __forceinline__ Pending issue(double, const double (&z)[1][NVX]) const {
-    Pending p;
-    sh->Y[lane] = z[0][NV];
-    SBM_LDS_FENCE();
-#pragma unroll
-    for (int s = 0; s < M::RL_MAXYS; ++s) p.ys[s] = sh->Y[yidx[s]];
-    SBM_LDS_FENCE();
-    return p;
+    return rows.exchange(sh->Y, lane, &z[0][NV]);
   }
   __device__ __forceinline__ Token eval(const Pending& p, double t) const {
     Token k;
     double jy[M::RL_MAXJY], jp[M::RL_MAXJP];
-    k.f = 0.0;
-#pragma unroll
-    for (int s = 0; s < M::RL_MAXJY; ++s) jy[s] = 0.0;
-#pragma unroll
-    for (int s = 0; s < M::RL_MAXJP; ++s) jp[s] = 0.0;
-    M::class_dispatch(cls, t, p.ys, ps, k.f, jy, jp);
-    k.f = cls >= 0 ? k.f : 0.0;
+    rows.template eval<true>(0, t, p, k.f, jy, jp);
     SBM_LDS_FENCE();
 #pragma unroll
     for (int s = 0; s < M::RL_MAXJY; ++s) sh->JD[jdpos[s]] = jy[s];
@@ -187,12 +175,7 @@ __global__ void __launch_bounds__(64, SbmMfmaPlan<M>::MIN_WAVES) sbm_sens_mfma_k
   sys.cbase = cbase;
   const bool has_row = lane < MNV;
   const int row = has_row ? lane : 0;
-  sys.cls = has_row ? M::rl_class(row) : -1;
-  const double* P = a.P + (size_t)traj * M::NP;
-#pragma unroll
-  for (int s = 0; s < M::RL_MAXYS; ++s) sys.yidx[s] = M::rl_ys(s, row);
-#pragma unroll
-  for (int s = 0; s < M::RL_MAXPS; ++s) sys.ps[s] = P[M::rl_ps(s, row)];
+  SBM_ROW_TABLE_LOAD(M, sys.rows, 0, a.P + (size_t)traj * M::NP, row, has_row, 0)
 #pragma unroll
   for (int s = 0; s < M::RL_MAXJY; ++s) {
     const int c = M::rl_jycol(s, row);

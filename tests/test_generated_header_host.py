@@ -1,5 +1,5 @@
 """The generated HIP header on the host: it is plain C++ once the device qualifiers and the few macros of
-csrc/sbm_integrators.hpp are defined away, so its members can be compiled with g++ and called through ctypes -- no GPU.
+csrc/sbm_wave.hpp are defined away, so its members can be compiled with g++ and called through ctypes -- no GPU.
 Checked here, on random networks (lower-triangular ones with several sub-diagonal entries and several J_p entries per
 row -- patterns the zoo models do not have -- and general ones with feedback):
 

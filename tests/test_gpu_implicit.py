@@ -1,7 +1,7 @@
 """Implicit midpoint on the GPU (BASELINE configs[4]: stiff 50-state cascade, N = 2550 coupled ODEs).
 
 Two levels of parity:
-  * scheme level: csrc/sbm_integrators.hpp::sbm_imid_kernel against oracle/imid_oracle.py, the same
+  * scheme level: csrc/sbm_implicit_midpoint.hpp::sbm_imid_kernel against oracle/imid_oracle.py, the same
     algorithm in dense numpy (same steps, same Newton recipe): agreement to rounding;
   * reference level: against SciPy odeint (LSODA switches to BDF on this system) -- second-order
     convergence of the raw scheme and agreement of the Richardson-extrapolated result.

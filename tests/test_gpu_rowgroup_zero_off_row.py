@@ -1,5 +1,5 @@
 """Lanes of the row-group kernels that evaluate no row get all-zero operands instead of a select behind every row evaluation
-where the model's class bodies vanish on them (RL_F_ZERO_OFF_ROW, csrc/sbm_integrators.hpp RowGroupSystem::kZeroOffRow).
+where the model's class bodies vanish on them (RL_F_ZERO_OFF_ROW, csrc/sbm_kernels_rowgroup.hpp RowGroupSystem::kZeroOffRow).
 That changes no floating-point operation of any lane with a row: the default build returns the same BITS for Y, S,
 n_steps, n_reject and status as the plugin built with -DSBM_RG_KEEP_F_SELECT=1 (the select: the code before), NaN rows
 included.  The cases are in tests/support/zero_off_row_cases.py.  The twin plugins are compiled by build(); they run in

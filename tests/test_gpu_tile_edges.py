@@ -1,4 +1,4 @@
-"""sbm_sens_mfma_kernel (csrc/sbm_sens_mfma.hpp) and sbm_sens_packed_kernel (csrc/sbm_integrators.hpp) at every tile and
+"""sbm_sens_mfma_kernel (csrc/sbm_sens_mfma.hpp) and sbm_sens_packed_kernel (csrc/sbm_kernels_rowlane.hpp) at every tile and
 segment edge: the ten models of models_zoo.tile_edge_specs(), each forced onto every one of the two kernels that takes
 it.  Which instantiation a model compiles -- RT, CT, NCH, LDJ, LDA; SEG and trajectories per wavefront -- is computed
 and held against a literal table on the CPU (tests/test_tile_edge_layouts_cpu.py::EXPECTED).

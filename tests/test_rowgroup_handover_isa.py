@@ -1,4 +1,4 @@
-"""The per-stage operand hand-over of the row-group kernels (SBM_RG_EARLY_STAGES, csrc/sbm_integrators.hpp) in the ISA:
+"""The per-stage operand hand-over of the row-group kernels (SBM_RG_EARLY_STAGES, csrc/sbm_kernels_rowgroup.hpp) in the ISA:
 the default build of a plugin against its -DSBM_RG_EARLY_STAGES=0 twin (every stage fetches its operands in finish).
 Both are compiled by build(); the code objects are read with the extraction of tests/test_rowgroup_kernel_isa.py, no GPU.
 
@@ -102,7 +102,7 @@ def valu_under_the_operand_fetch(body):
 
 def default_mask():
     """the stages the default build of cascade20 / RG0 fetches early, from the source"""
-    with open(os.path.join(REPO, 'sysbio_modeling_amd', 'csrc', 'sbm_integrators.hpp')) as fh:
+    with open(os.path.join(REPO, 'sysbio_modeling_amd', 'csrc', 'sbm_kernels_rowgroup.hpp')) as fh:
         m = re.search(r'^#define SBM_RG_EARLY_DEFAULT\s+(0[xX][0-9a-fA-F]+|\d+)u?\s*$', fh.read(), re.M)
     assert m, "SBM_RG_EARLY_DEFAULT not found"
     return int(m.group(1), 0)

@@ -1,7 +1,7 @@
 """RL_F_ZERO_OFF_ROW of the model headers (symbolic/emit_rowlane.py::f_zero_off_row): whether every class body gives
 f == 0 exactly, through finite intermediates, when all its state and parameter operands are 0.  Where it is true the
 row-group kernels hand all-zero operands to the lanes that evaluate no row and drop the select that zeroed their f
-(csrc/sbm_integrators.hpp, RowGroupSystem::kZeroOffRow); where it is false nothing changes.  No GPU needed.
+(csrc/sbm_kernels_rowgroup.hpp, RowGroupSystem::kZeroOffRow); where it is false nothing changes.  No GPU needed.
 
 The emitter decides on the expressions it prints, in exact arithmetic; the last test evaluates the classes' f in Python
 floats at zeros instead (a reciprocal of 0 raises ZeroDivisionError there, 0/0 too) and asks for the same answer."""
