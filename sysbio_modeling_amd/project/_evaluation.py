@@ -1,11 +1,14 @@
 """What every host loop around the project kernels shares (project/fitting.py, project/ensembles.py, base_project.py): the
-one place that calls ``sbm_residuals_batch`` / ``sbm_jacobian_batch``, the output set those calls fill, and the three small
-rules the loops apply to what comes back.  torch is imported inside the functions: the module loads without a GPU."""
+one place that calls ``sbm_residuals_batch`` / ``sbm_jacobian_batch``, the output set those calls fill, the three small
+rules the loops apply to what comes back, and the other per-step device calls of the loops (``trust_step``, ``mh_propose``,
+``mh_accept``, ``sampling_axes``), each written once.  torch is imported inside the functions: it loads without a GPU."""
 from __future__ import annotations
 
 import ctypes
 
 from .. import _control, _lib
+
+p = _lib.dev_ptr          # void* of a device tensor; None is NULL
 
 
 class DeviceEvaluator(object):
@@ -48,7 +51,6 @@ class DeviceEvaluator(object):
         """Integrate the rows of ``theta`` (n, q), float64 and contiguous on the device, with the options ``opts``
         (``Project._opts``) into ``buf``: ``sbm_jacobian_batch`` with ``jacobian``, else ``sbm_residuals_batch``.  An
         output ``buf`` does not hold is not computed.  Enqueues only."""
-        p = _lib.dev_ptr
         n = int(theta.shape[0])
         sf = p(buf['sf']) if self.G else None
         if jacobian:
@@ -86,3 +88,64 @@ def inverse_row_sigma(project):
     """1 / sigma per measurement row (numpy) where the project's Jacobian comes undivided by it (``reference_compat``,
     SURVEY 8a quirk 3), else None."""
     return 1.0 / project.descriptor_arrays()['row_sigma'] if project.reference_compat else None
+
+
+# ---------------------------------------------------------------------------------------------
+# The per-step device calls of the fit and sampler loops.  Every pointer of the C ABI is a void*: the order of the
+# tensors is checked here and nowhere else (tests/test_gpu_device_steps.py), so the loops pass them by name.  ``ctx`` is
+# the ``_lib.Context`` whose stream the launch goes to; sizes are read from the shapes; None is NULL; enqueue only.
+# ---------------------------------------------------------------------------------------------
+def trust_step(ctx, *, J, r, dscale, radius, lam, delta, pred, dxnorm, status, row_scale=None, skip=None, max_step=0.0,
+               theta=None, trial=None, gtx=None, held=None, lower=None, upper=None):
+    """One trust-region step per start from J (V, M, q) and r (V, M): ``sbm_lm_trust_step_bounded`` with ``lower`` /
+    ``upper`` (V, q), else ``sbm_lm_trust_step_held`` with the int32 mask ``held`` (V, q) or NULL, which is
+    ``sbm_lm_trust_step_ex`` -- the same kernel, the same bits.  Without ``theta`` / ``trial`` / ``gtx`` / ``skip`` /
+    ``row_scale`` it is ``sbm_lm_trust_step``.  include/sbm.h says what each tensor holds."""
+    V, M, q = J.shape
+    args = (ctx.handle, p(J), p(r), p(dscale), p(radius), p(lam), V, M, q, p(row_scale), p(skip), float(max_step), p(theta),
+            p(trial), p(delta), p(pred), p(dxnorm), p(gtx), p(status), p(held))
+    if lower is not None or upper is not None:
+        _lib.check(ctx.lib.sbm_lm_trust_step_bounded(*args, p(lower), p(upper), None), 'sbm_lm_trust_step_bounded')
+    else:
+        _lib.check(ctx.lib.sbm_lm_trust_step_held(*args), 'sbm_lm_trust_step_held')
+
+
+def mh_propose(ctx, *, curr, samp, z, trial, held=None, lower=None, upper=None, outside=None):
+    """trial = curr + samp z for C chains: ``samp`` (q, q) shared or (C, q, q) one matrix per chain.  With the int32 flags
+    ``outside`` (C,) ``sbm_mh_propose_box`` (``held`` int32 (C, q), ``lower`` / ``upper`` (C, q), each nullable), else
+    ``sbm_mh_propose``: two kernels, so the choice is made here."""
+    C, q = curr.shape
+    per_chain = int(samp.dim() == 3)
+    if outside is not None:
+        _lib.check(ctx.lib.sbm_mh_propose_box(ctx.handle, p(curr), p(samp), per_chain, p(z), C, q, p(held), p(lower), p(upper),
+                                              p(trial), p(outside)), 'sbm_mh_propose_box')
+    else:
+        _lib.check(ctx.lib.sbm_mh_propose(ctx.handle, p(curr), p(samp), per_chain, p(z), C, q, p(trial)), 'sbm_mh_propose')
+
+
+def mh_accept(ctx, *, norms, status, log_u, temperature, trial, curr, F_curr, n_accepted, entropy=None, ens_slot=None,
+              ens_F_slot=None, veto=None, axes_curr=None, axes_trial=None, axes_status=None):
+    """Accept or reject the C trial points and move ``curr`` / ``F_curr`` / ``n_accepted`` (and the record slots, when
+    given): ``sbm_mh_accept_ex``, or with ``axes_curr`` / ``axes_trial`` = (V, s, samp) of the candidate density at the two
+    ends and the trial axes' ``axes_status`` ``sbm_mh_accept_hastings_ex``, which moves the axes with the point.  ``veto``
+    int32 (C,) or NULL: the unsuffixed entry points are these with NULL."""
+    C, q = curr.shape
+    args = (ctx.handle, p(norms), p(status), p(entropy), p(log_u), float(temperature), C, q, p(trial), p(curr), p(F_curr),
+            p(n_accepted), p(ens_slot), p(ens_F_slot))
+    if axes_curr is not None:
+        _lib.check(ctx.lib.sbm_mh_accept_hastings_ex(*args, *(p(a) for a in axes_curr), *(p(a) for a in axes_trial),
+                                                     p(axes_status), p(veto)), 'sbm_mh_accept_hastings_ex')
+    else:
+        _lib.check(ctx.lib.sbm_mh_accept_ex(*args, p(veto)), 'sbm_mh_accept_ex')
+
+
+def sampling_axes(ctx, *, status, cutoff, temperature, step_scale, J=None, row_scale=None, H=None, eig=None, V=None, s=None,
+                  samp=None, held=None):
+    """Axes of the candidate density of the C = len(status) chains, ``sbm_sampling_axes_held`` (``held`` int32 (C, q) or
+    NULL, which is ``sbm_sampling_axes``): from exactly one of the Jacobians ``J`` (C, M, q) (with ``row_scale`` (M,) or
+    NULL) and the Hessian ``H`` (q, q) for all chains or (C, q, q); the outputs ``eig``, ``V``, ``s``, ``samp`` as given."""
+    _lib.check(ctx.lib.sbm_sampling_axes_held(ctx.handle, p(J), p(row_scale), p(H), int(H is not None and H.dim() == 3),
+                                              int(status.shape[0]), int(J.shape[-2]) if J is not None else 0,
+                                              int((J if J is not None else H).shape[-1]),
+                                              float(cutoff), float(temperature), float(step_scale), p(eig), p(V), p(s), p(samp),
+                                              p(status), p(held)), 'sbm_sampling_axes_held')

@@ -14,7 +14,7 @@ from __future__ import annotations
 import numpy as np
 
 from .. import _lib
-from ._evaluation import DeviceEvaluator, finite_cost, inverse_row_sigma, one_device_call, usable
+from ._evaluation import DeviceEvaluator, finite_cost, inverse_row_sigma, one_device_call, trust_step, usable
 
 
 def _trial_budget(project, th, integrator_overrides, n_steps_sum=None, status=None):
@@ -265,6 +265,29 @@ def _median_over(live):
     return lambda t: float(t[live].median()) if some else 0.0
 
 
+def _traced_launch(integrate_trial, project, ev, tr, done, st, bounded):
+    """``trace`` of the fused loop: ``integrate_trial()`` between two synchronisations and the ``launch`` dict of the history entry,
+    what the launch cost and why -- it lasts as long as its slowest trajectory (scripts/dev_fit_trace.py).  ``bounded``: ``st``
+    is the step status of a bounded fit, which says what steps the bounds took away."""
+    import time
+    import torch
+    torch.cuda.synchronize(ev.dev)
+    t_launch = time.perf_counter()
+    integrate_trial()
+    torch.cuda.synchronize(ev.dev)
+    t_launch = time.perf_counter() - t_launch
+    V = int(done.shape[0])
+    per = torch.empty((V, max(1, len(project._experiments))), dtype=torch.int32, device=ev.dev)
+    _lib.check(ev.lib.sbm_project_trajectory_steps(ev.proj, V, _lib.dev_ptr(per)), 'sbm_project_trajectory_steps')
+    launch = dict(ms=1e3 * t_launch, steps_max=int(per.max()), steps_mean=float(per.double().mean()),
+                  steps_p99=float(per.double().flatten().quantile(0.99)), failed=int((tr['status'] != 0).sum()),
+                  done=int((done != 0).sum()))
+    if bounded:
+        # projected steps that did not descend (status 4), each a spent iteration
+        launch['no_descent'] = int(((st == 4) & (done == 0)).sum())
+    return launch
+
+
 def _result(th, cost, n_iter, done, n_eval, n_jac, history=None, held=None, bounds=None):
     """The dict `levenberg_marquardt_batch` returns, from the loop's device tensors"""
     import torch
@@ -323,7 +346,7 @@ def levenberg_marquardt_batch(project, thetas0, max_iter=60, lambda0=1e-2, lambd
     the problem without the held columns (``sbm_lm_trust_step_held`` compacts the system per start: holding 60 of 68
     parameters costs an 8 x 8 factorisation); the returned ``theta[:, held]`` is ``thetas0[:, held]`` bit for bit, a start
     with nothing free comes back as it came, converged.  Supported with ``algorithm='trust_region'`` and an integration
-    that is one device call; ``held=None`` is the loop as it was.
+    that is one device call; ``held=None`` is the loop as it was: the same kernels, the same bits.
 
     ``bounds``: a box the fitted parameters stay in, in the units of ``thetas0`` (log parameters) -- ``(lower, upper)``, each
     a scalar, an array (q,) or (V, q), infinite where a side is open; or a dict ``{(p_group, settings): (lo, hi)}`` whose
@@ -333,8 +356,8 @@ def levenberg_marquardt_batch(project, thetas0, max_iter=60, lambda0=1e-2, lambd
     gradient pushing outward is held for that step, the step on the others is lmder's and is projected into the box, so an
     iterate that reaches a bound lies ON it bit for bit.  A projected step that no longer descends in the model is not taken
     and costs that iteration (the radius is halved); a start whose free parameters all sit on bounds with the gradient
-    pushing outward has converged.  Same support as ``held``; ``bounds=None`` is the loop as it was, the same entry points
-    included.
+    pushing outward has converged.  Same support as ``held``; ``bounds=None`` is the loop as it was: the same kernels, the same
+    bits.
 
     With a handful of starts the chip is mostly empty: ``variant='small_batch'`` (an integrator override) lets the
     sensitivity kernel use its small-batch split while starts x experiments x chunks <= 2048.
@@ -443,7 +466,6 @@ def _trust_region_batch(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
     th, V, q, dev, lib, ctx, lazy_jacobian = _prepare(project, thetas0, lazy_jacobian)
     f64, i32 = torch.float64, torch.int32
     evaluate, cost_only, r, J, cost = _evaluated_starts(project, th, integrator_overrides, warn=True)
-    M = r.shape[1]
     done = ~torch.isfinite(cost)
     dscale = torch.zeros((V, q), dtype=f64, device=dev)
     lam = torch.zeros((V,), dtype=f64, device=dev)
@@ -455,7 +477,6 @@ def _trust_region_batch(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
     n_iter = torch.full((V,), int(max_iter), dtype=torch.int64, device=dev)
     n_eval, n_jac = V, V
     history = []
-    p = _lib.dev_ptr
     first = True
     for it in range(max_iter):
         Jc, rc = _finite_stand_ins(J, r, cost)
@@ -465,8 +486,7 @@ def _trust_region_batch(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
             d0 = torch.where(col > 0, col, torch.ones_like(col))
             xn = (d0 * th).norm(dim=1)
             radius = torch.where(xn > 0, factor * xn, torch.full_like(xn, float(factor)))
-        _lib.check(lib.sbm_lm_trust_step(ctx.handle, p(Jc), p(rc), p(dscale), p(radius), p(lam), V, M, q, p(delta), p(pred),
-                                         p(dxnorm), p(st)), 'sbm_lm_trust_step')
+        trust_step(ctx, J=Jc, r=rc, dscale=dscale, radius=radius, lam=lam, delta=delta, pred=pred, dxnorm=dxnorm, status=st)
         step = delta.clamp(-max_step, max_step)
         clipped = (step != delta).any(dim=1)
         if bool(clipped.any()):
@@ -540,19 +560,19 @@ def _trust_region_batch(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
 
 def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.49012e-8, factor=100.0, trace=False,
                         lazy_jacobian='auto', max_step=2.0, held=None, bounds=None, **integrator_overrides):
-    """`_trust_region_batch` with the bookkeeping on the device: per iteration ONE ``sbm_lm_trust_step_ex`` (lmpar, the
+    """`_trust_region_batch` with the bookkeeping on the device: per iteration ONE ``_evaluation.trust_step`` (lmpar, the
     clipped step and the trial point), the integration of the trial points (``sbm_jacobian_batch`` /
     ``sbm_residuals_batch`` into preallocated buffers), ONE ``sbm_lm_update`` (lmder's ratio / radius / acceptance /
     convergence logic) and ONE ``sbm_lm_accept`` (the accepted points' theta, r, J, cost) -- about eight launches and one
     4-byte read-back where round 2's loop issued ~70 tensor selects (68 000 micro-launches in a 100-iteration fit,
     profiles/r02/fit_kernel_stats.csv).  Same algorithm, same numbers up to the order of a few sums.
 
-    ``held`` (see `levenberg_marquardt_batch`): the step comes from ``sbm_lm_trust_step_held`` with the (V, q) mask, the
+    ``held`` (see `levenberg_marquardt_batch`): ``trust_step`` gets the (V, q) mask (``sbm_lm_trust_step_held``), the
     initial radius factor * ||D theta|| is that of the free parameters, and a start with nothing free is done before the
     first step.  ``sbm_lm_update`` and ``sbm_lm_accept`` are called as ever: held columns have dscale = 0 and
     trial = theta.
 
-    ``bounds``: the step comes from ``sbm_lm_trust_step_bounded`` (with the held mask, or NULL), which chooses the active set
+    ``bounds``: ``trust_step`` gets the box (``sbm_lm_trust_step_bounded``, with the held mask or NULL), which chooses the active set
     from this iteration's gradient on the device: no read-back is added.  Its status 3 (a constrained stationary point)
     ends a start in ``sbm_lm_update``; its status 4 (a projected step that does not descend) halves the radius there."""
     import torch
@@ -607,38 +627,17 @@ def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
     n_eval, n_jac = V, V
     history = []
     held_i32 = held_dev.to(i32).contiguous() if held_dev is not None else None
-    for it in range(max_iter):
-        if lower_dev is not None:
-            _lib.check(lib.sbm_lm_trust_step_bounded(ctx.handle, p(cur_J), p(cur_r), p(dscale), p(radius), p(lam), V, M, q,
-                                                     p(row_scale), p(done), float(max_step), p(th), p(trial), p(delta), p(pred),
-                                                     p(dxnorm), p(gtx), p(st), p(held_i32), p(lower_dev), p(upper_dev), None),
-                       'sbm_lm_trust_step_bounded')
-        elif held_i32 is None:
-            _lib.check(lib.sbm_lm_trust_step_ex(ctx.handle, p(cur_J), p(cur_r), p(dscale), p(radius), p(lam), V, M, q,
-                                                p(row_scale), p(done), float(max_step), p(th), p(trial), p(delta), p(pred),
-                                                p(dxnorm), p(gtx), p(st)), 'sbm_lm_trust_step_ex')
-        else:
-            _lib.check(lib.sbm_lm_trust_step_held(ctx.handle, p(cur_J), p(cur_r), p(dscale), p(radius), p(lam), V, M, q,
-                                                  p(row_scale), p(done), float(max_step), p(th), p(trial), p(delta), p(pred),
-                                                  p(dxnorm), p(gtx), p(st), p(held_i32)), 'sbm_lm_trust_step_held')
-        if trace:
-            import time
-            torch.cuda.synchronize(dev)
-            t_launch = time.perf_counter()
+
+    def integrate_trial():
         ev.run(trial, opts_t, tr, not lazy_jacobian)
+
+    for it in range(max_iter):
+        trust_step(ctx, J=cur_J, r=cur_r, dscale=dscale, radius=radius, lam=lam, row_scale=row_scale, skip=done, max_step=max_step,
+                   theta=th, trial=trial, delta=delta, pred=pred, dxnorm=dxnorm, gtx=gtx, status=st, held=held_i32,
+                   lower=lower_dev, upper=upper_dev)
+        # the integration of the trial points (launch: the trace's record of it, None without trace)
+        launch = _traced_launch(integrate_trial, project, ev, tr, done, st, lower_dev is not None) if trace else integrate_trial()
         n_eval += V
-        if trace:
-            # what the trial launch cost and why: it lasts as long as its slowest trajectory (scripts/dev_fit_trace.py)
-            torch.cuda.synchronize(dev)
-            t_launch = time.perf_counter() - t_launch
-            per = torch.empty((V, max(1, len(project._experiments))), dtype=i32, device=dev)
-            _lib.check(lib.sbm_project_trajectory_steps(ev.proj, V, p(per)), 'sbm_project_trajectory_steps')
-            launch = dict(ms=1e3 * t_launch, steps_max=int(per.max()), steps_mean=float(per.double().mean()),
-                          steps_p99=float(per.double().flatten().quantile(0.99)), failed=int((tr['status'] != 0).sum()),
-                          done=int((done != 0).sum()))
-            if lower_dev is not None:
-                # steps the bounds took away: projected steps that did not descend (status 4), each a spent iteration
-                launch['no_descent'] = int(((st == 4) & (done == 0)).sum())
         cost_prev = cost.clone() if trace else None
         _lib.check(lib.sbm_lm_update(ctx.handle, p(cost), p(tr['norms']), p(tr['status']), p(pred), p(dxnorm), p(gtx), p(st),
                                      p(th), p(dscale), V, q, float(ftol), float(xtol), it, 1 if it == 0 else 0, p(radius),
