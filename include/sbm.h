@@ -490,6 +490,37 @@ int sbm_lm_trust_step_bounded(sbm_ctx* ctx, const double* J_dev, const double* r
                               double* dxnorm_dev, double* gtx_dev, int32_t* status_dev, const int32_t* held_dev,
                               const double* lower_dev, const double* upper_dev, int32_t* active_out_dev);
 
+/* Geodesic acceleration of the step a trust-step call just produced (Transtrum and Sethna, "Improvements to the
+ * Levenberg-Marquardt algorithm", 2012; project/fitting.py `geodesic=`).  An added export: SBM_ABI_VERSION is unchanged.
+ * Called between sbm_lm_trust_step_ex / _held and the integration of the trial points, with the step's own J, r, row_scale,
+ * skip, held, max_step and theta, the dscale and lambda it left, and its status (step_status).  v = delta on entry.
+ *   r_base, r_probe [V][M]   residuals at theta and at theta + h v, from ONE state-only integration of both (r_base
+ *                            nullable: r is used); status_base, status_probe [V] nullable: their integration status
+ *   1. r_vv = (2 / h) ((r_probe - r_base) / h - J~ v), J~ = diag(row_scale) J: the second directional derivative of the
+ *      residuals along v
+ *   2. (J~^T J~ + lambda D^2) a = -J~^T r_vv by Cholesky: the matrix the step came from
+ *   3. rho = 2 ||D a|| / ||D v||; the acceleration is applied iff ||D a|| > 0 and rho <= alpha
+ *   4. x = v + a / 2, every component clipped to +-max_step when that is > 0; delta = x, trial = theta + x,
+ *      dxnorm = ||D x||, gtx = g . x, pred = -gtx - x^T J~^T J~ x / 2: the quantities of the step TAKEN, as the trust step
+ *      reports them for a clipped step -- unless that step does not descend in the model (not gtx < 0 and pred > 0)
+ *   accel_status [V]  out    0 applied; 1 no step to accelerate (skip != 0, step_status != 0, nothing free); 2 probe
+ *                            unusable (a status != 0, a non-finite entry of r_base / r_probe); 3 non-finite J or r, or the
+ *                            damped matrix does not factor; 4 the gate (rho > alpha, or a = 0); 5 no descent
+ *   ratio_out [V]     nullable, out: rho where it was computed (status 0, 4, 5), NaN elsewhere
+ *   n_accel [V]       nullable, in / out: += 1 where accel_status = 0
+ * Wherever accel_status != 0, delta, trial, pred, dxnorm and gtx keep the bits the trust step wrote; lambda and dscale
+ * are never written.  held != NULL compacts the system exactly as sbm_lm_trust_step_held does (the arithmetic of the call
+ * on the arrays with the held columns deleted); a = 0 on a column that is not free, whose delta and trial are left alone.
+ * Refused with SBM_E_ARG: h <= 0, alpha < 0 (or NaN), q > 128, a q whose LDS does not fit (as for the trust step; q = 128
+ * fits with a 16-row tile).  One pass over J and one q x q factorisation per vector. */
+int sbm_lm_geodesic(sbm_ctx* ctx, const double* J_dev, const double* r_dev, const double* r_base_dev,
+                    const double* r_probe_dev, const int32_t* status_base_dev, const int32_t* status_probe_dev,
+                    const double* dscale_dev, const double* lambda_dev, int32_t V, int32_t M, int32_t q,
+                    const double* row_scale_dev, const int32_t* skip_dev, const int32_t* step_status_dev,
+                    const int32_t* held_dev, double h, double alpha, double max_step, const double* theta_dev,
+                    double* delta_dev, double* trial_dev, double* pred_dev, double* dxnorm_dev, double* gtx_dev,
+                    int32_t* accel_status_dev, double* ratio_dev, int32_t* n_accel_dev);
+
 /* lmder's bookkeeping between two steps (MINPACK lmder.f, the loop around lmpar: what scipy.optimize.leastsq -- the
  * reference's optimiser, tests/test_Project.py:202-213, 351-357 -- does after every function evaluation), for V starts
  * in one launch: actual and predicted relative reduction, their ratio, the radius / lambda update (ratio <= 1/4: shrink

@@ -101,6 +101,9 @@ SIGNATURES = {
                                               _vp, _vp, _vp, _vp, _vp, _vp]),
     'sbm_lm_trust_step_bounded': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, ctypes.c_double, _vp,
                                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sbm_lm_geodesic': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                       ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp]),
     'sbm_lm_update': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, ctypes.c_double,
                                      ctypes.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sbm_lm_accept': (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

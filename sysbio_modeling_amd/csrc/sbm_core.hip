@@ -12,6 +12,8 @@
 //                           sbm_loss_eval_host verify of a descriptor before they touch the device (plain C++, no HIP)
 //   sbm_lm.hpp              k_lm_step, k_lm_trust[_held|_bounded], k_lm_update, k_lm_accept: the fitting loop (batched Levenberg-Marquardt
 //                           step, lmder's trust-region step and bookkeeping)
+//   sbm_lm_geodesic.hpp     k_lm_geodesic: the second-order (geodesic) correction of the trust-region step, on sbm_lm.hpp's
+//                           builder of the normal equations and its factorisation
 //   sbm_sampler.hpp         k_sf_entropy, k_mh_propose[_box], k_mh_accept, k_mh_accept_hastings: scale-factor entropy integrals
 //                           (linear_scale_factor.py:63-81; the quadrature rule: sbm_sf_quadrature.hpp), candidate move and
 //                           the two acceptance rules of the multi-chain sampler (project/Ensembles.py:193-198, 200-264)
@@ -38,6 +40,7 @@
 #include "sbm_chain_diagnostics.hpp"
 #include "sbm_ensemble_stats.hpp"
 #include "sbm_lm.hpp"
+#include "sbm_lm_geodesic.hpp"
 #include "sbm_project_check.hpp"
 #include "sbm_sampler.hpp"
 #include "sbm_sampling_axes.hpp"
@@ -914,6 +917,31 @@ extern "C" int sbm_lm_trust_step(sbm_ctx* ctx, const double* J, const double* r,
                                  double* dxnorm, int32_t* status) {
   return sbm_lm_trust_step_ex(ctx, J, r, dscale, radius, lambda, V, M, q, nullptr, nullptr, 0.0, nullptr, nullptr, delta, pred,
                               dxnorm, nullptr, status);
+}
+
+// The geodesic acceleration of the step a trust-step call just produced (kernel: sbm_lm_geodesic.hpp).  held = NULL:
+// k_lm_geodesic<false>, else the compacting instantiation.  The kernel's static LDS (LM_GEO_STATIC_LDS) is taken off the
+// limit the row tile is chosen for, as for the held trust step.
+extern "C" int sbm_lm_geodesic(sbm_ctx* ctx, const double* J, const double* r, const double* r_base, const double* r_probe,
+                               const int32_t* status_base, const int32_t* status_probe, const double* dscale,
+                               const double* lambda, int32_t V, int32_t M, int32_t q, const double* row_scale,
+                               const int32_t* skip, const int32_t* step_status, const int32_t* held, double h, double alpha,
+                               double max_step, const double* theta, double* delta, double* trial, double* pred,
+                               double* dxnorm, double* gtx, int32_t* accel_status, double* ratio_out, int32_t* n_accel) {
+  if (!ctx || !J || !r || !r_probe || !dscale || !lambda || !step_status || !theta || !delta || !trial || !pred || !dxnorm || !gtx ||
+      !accel_status)
+    return sbm_fail(SBM_E_ARG, "sbm_lm_geodesic: NULL argument");
+  if (V < 0 || M <= 0 || q <= 0 || q > LM_MAX_Q) return sbm_fail(SBM_E_ARG, "sbm_lm_geodesic: bad sizes V=%d M=%d q=%d (q <= %d)", V, M, q, LM_MAX_Q);
+  if (!(h > 0.0) || !(h < 1.0e300)) return sbm_fail(SBM_E_ARG, "sbm_lm_geodesic: the probe length h = %g has to be positive", h);
+  if (!(alpha >= 0.0)) return sbm_fail(SBM_E_ARG, "sbm_lm_geodesic: the gate alpha = %g has to be >= 0", alpha);
+  if (V == 0) return 0;
+  int tile = 0;
+  const size_t lds = lm_lds_bytes(q, 4, (size_t)lm_lds_limit(ctx) - LM_GEO_STATIC_LDS, &tile);
+  if (!lds) return sbm_fail(SBM_E_ARG, "sbm_lm_geodesic: q = %d does not fit the %d KB of LDS of a workgroup", q, lm_lds_limit(ctx) / 1024);
+  LmGeodesicArgs a{J, r, r_base, r_probe, status_base, status_probe, dscale, lambda, row_scale, skip, step_status, theta, delta, trial,
+                   pred, dxnorm, gtx, accel_status, ratio_out, n_accel, h, alpha, max_step, M, q, tile};
+  if (held) return launch_lds(ctx, k_lm_geodesic<true>, dim3(V), dim3(256), lds, a, held);
+  return launch_lds(ctx, k_lm_geodesic<false>, dim3(V), dim3(256), lds, a, held);
 }
 
 extern "C" int sbm_lm_update(sbm_ctx* ctx, const double* cost, const double* norms_trial, const int32_t* status_trial,

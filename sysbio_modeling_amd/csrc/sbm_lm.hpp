@@ -1,6 +1,7 @@
 // sbm_lm.hpp -- kernels of the fitting loop (include/sbm.h: sbm_lm_step, sbm_lm_trust_step[_ex|_held|_bounded], sbm_lm_update,
-// sbm_lm_accept).  The two step kernels share the builder of the normal equations (lm_normal_equations) and the
-// factorisation (lm_cholesky / lm_forward / lm_backward); the host wrappers with the argument checks are in sbm_core.hip.
+// sbm_lm_accept).  The step kernels and the geodesic acceleration (sbm_lm_geodesic.hpp) share the builder of the normal
+// equations (lm_normal_equations), the list of free columns (lm_free_columns) and the factorisation (lm_cholesky /
+// lm_forward / lm_backward); the host wrappers with the argument checks are in sbm_core.hip.
 #ifndef SBM_LM_HPP
 #define SBM_LM_HPP
 
@@ -38,10 +39,25 @@ struct LmTriangle {
 // (T: [TILE][ld], rt: [TILE]).  *s_bad, in LDS and zeroed by the caller, is set on a non-finite entry; ends on a barrier.
 // GATHER: the system is built from the q columns idx[0..q) (in LDS, written before the call) of a J with rows of qs entries
 // -- column c of the tile is column idx[c] of J, everything after the staging is the same code on the same numbers.
-template <bool GATHER = false>
+// SECOND (sbm_lm_geodesic.hpp): a second right-hand side from the same pass, see LmSecondRhs; without it the code is the
+// code it was.
+struct LmSecondRhs {
+  const double* vv;       // [q]    LDS, written before the call: the step v the second derivative is taken along
+  const double* r_base;   // [M]    residuals at theta and at theta + h v, from one state-only integration
+  const double* r_probe;  // [M]
+  double* rvv;            // [TILE] LDS: the staged rows' r_vv = (2 / h) ((r_probe - r_base) / h - (J v)_m)
+  int* s_bad;             // LDS, zeroed by the caller: set on a non-finite entry of r_base / r_probe
+  double h;
+  double acc;             // out: thread c < q owns (J^T r_vv)[c]
+};
+constexpr int LM_ROW_LANES = 8;   // threads that share one staged row's J v: 256 threads, LM_TILE rows
+static_assert(LM_TILE * LM_ROW_LANES <= 256, "one lane group per staged row");
+
+template <bool GATHER = false, bool SECOND = false>
 __device__ __forceinline__ void lm_normal_equations(LmTriangle& n, int& n_own, double& gacc, const double* Jv, const double* rv,
                                                     const double* row_scale, int M, int q, int TILE, double* T, double* rt,
-                                                    int* s_bad, int tid, int qs = 0, const short* idx = nullptr) {
+                                                    int* s_bad, int tid, int qs = 0, const short* idx = nullptr,
+                                                    [[maybe_unused]] LmSecondRhs* second = nullptr) {
   const int ld = q + 1, n_low = q * (q + 1) / 2;
   n_own = 0;
   for (int e = tid; e < n_low; e += 256) {
@@ -68,6 +84,22 @@ __device__ __forceinline__ void lm_normal_equations(LmTriangle& n, int& n_own, d
       if (!(fabs(val) < 1.0e300)) *s_bad = 1;
     }
     __syncthreads();
+    if constexpr (SECOND) {
+      // (J v)_m of staged row m = tid / 8: eight strided fma chains over the columns, folded by a butterfly -- a shape that
+      // depends on q alone, not on the tile
+      const int rr = tid / LM_ROW_LANES, k = tid % LM_ROW_LANES;
+      double w = 0.0;
+      if (rr < rows)
+        for (int c = k; c < q; c += LM_ROW_LANES) w = fma(T[rr * ld + c], second->vv[c], w);
+#pragma unroll
+      for (int off = 1; off < LM_ROW_LANES; off <<= 1) w += __shfl_xor(w, off, 64);
+      if (rr < rows && k == 0) {
+        const double rb = second->r_base[m0 + rr], rp = second->r_probe[m0 + rr];
+        if (!(fabs(rb) < 1.0e300) || !(fabs(rp) < 1.0e300)) *second->s_bad = 1;
+        second->rvv[rr] = (2.0 / second->h) * ((rp - rb) / second->h - w);
+      }
+      __syncthreads();
+    }
     for (int k = 0; k < n_own; ++k) {
       double s = n.acc[k];
       for (int rr = 0; rr < rows; ++rr) s = fma(T[rr * ld + n.oi[k]], T[rr * ld + n.oj[k]], s);
@@ -77,9 +109,28 @@ __device__ __forceinline__ void lm_normal_equations(LmTriangle& n, int& n_own, d
       double s = gacc;
       for (int rr = 0; rr < rows; ++rr) s = fma(T[rr * ld + tid], rt[rr], s);
       gacc = s;
+      if constexpr (SECOND) {
+        double s2 = second->acc;
+        for (int rr = 0; rr < rows; ++rr) s2 = fma(T[rr * ld + tid], second->rvv[rr], s2);
+        second->acc = s2;
+      }
     }
   }
   __syncthreads();
+}
+
+// The free columns of a vector in ascending order (is_free: this thread's column, false for tid >= the column count): a
+// ballot per wave (at most LM_MAX_Q = 128 columns: waves 0 and 1 have some), the waves' counts in LDS.  Writes
+// s_idx[0..n) and returns n, the same on every thread; the caller's next barrier publishes s_idx.
+__device__ __forceinline__ int lm_free_columns(bool is_free, short* s_idx, int* s_cnt /*[4]*/, int tid) {
+  const unsigned long long m = __ballot(is_free);
+  const int lane = tid & 63, wave = tid >> 6;
+  if (lane == 0) s_cnt[wave] = __popcll(m);
+  __syncthreads();
+  int base = 0;
+  for (int w = 0; w < wave; ++w) base += s_cnt[w];
+  if (is_free) s_idx[base + __popcll(m & ((1ull << lane) - 1ull))] = (short)tid;
+  return s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
 }
 
 // in-place right-looking Cholesky of the lower triangle of A (q x q, leading dimension ld) by the whole block; false if
@@ -272,7 +323,7 @@ __device__ __forceinline__ void lm_trust_body(LmTrustArgs a, const int32_t* held
   [[maybe_unused]] const short* idx = nullptr;
   if constexpr (HELD) {
     if (a.skip && a.skip[v]) { leave_alone(2); return; }
-    // the free columns in ascending order: a ballot per wave (qf <= 128: waves 0 and 1 have columns), the waves' counts in LDS
+    // the free columns in ascending order (lm_free_columns)
     __shared__ short s_idx[LM_MAX_Q];
     __shared__ int s_cnt[4];
     [[maybe_unused]] int code = 0;           // BOUNDED: this thread's column as active_out names it
@@ -311,14 +362,7 @@ __device__ __forceinline__ void lm_trust_body(LmTrustArgs a, const int32_t* held
     } else {
       is_free = tid < qf && held[(size_t)v * qf + tid] == 0;
     }
-    const unsigned long long m = __ballot(is_free);
-    const int lane = tid & 63, wave = tid >> 6;
-    if (lane == 0) s_cnt[wave] = __popcll(m);
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += s_cnt[w];
-    q = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    if (is_free) s_idx[base + __popcll(m & ((1ull << lane) - 1ull))] = (short)tid;
+    q = lm_free_columns(is_free, s_idx, s_cnt, tid);
     if (tid < qf && !is_free) a.dscale[(size_t)v * qf + tid] = 0.0;
     if (q == 0) {                            // (uniform)
       if constexpr (BOUNDED) {

@@ -1,6 +1,6 @@
 """What every host loop around the project kernels shares (project/fitting.py, project/ensembles.py, base_project.py): the
 one place that calls ``sbm_residuals_batch`` / ``sbm_jacobian_batch``, the output set those calls fill, the three small
-rules the loops apply to what comes back, and the other per-step device calls of the loops (``trust_step``, ``mh_propose``,
+rules the loops apply to what comes back, and the other per-step device calls of the loops (``trust_step``, ``geodesic_step``, ``mh_propose``,
 ``mh_accept``, ``sampling_axes``), each written once.  torch is imported inside the functions: it loads without a GPU."""
 from __future__ import annotations
 
@@ -108,6 +108,21 @@ def trust_step(ctx, *, J, r, dscale, radius, lam, delta, pred, dxnorm, status, r
         _lib.check(ctx.lib.sbm_lm_trust_step_bounded(*args, p(lower), p(upper), None), 'sbm_lm_trust_step_bounded')
     else:
         _lib.check(ctx.lib.sbm_lm_trust_step_held(*args), 'sbm_lm_trust_step_held')
+
+
+def geodesic_step(ctx, *, J, r, r_probe, dscale, lam, step_status, theta, delta, trial, pred, dxnorm, gtx, accel_status, h, alpha,
+                  r_base=None, status_base=None, status_probe=None, row_scale=None, skip=None, held=None, max_step=0.0,
+                  ratio=None, n_accel=None):
+    """``sbm_lm_geodesic``: the geodesic acceleration of the steps `trust_step` just wrote into ``delta`` / ``trial`` /
+    ``pred`` / ``dxnorm`` / ``gtx`` (with the same J, r, row_scale, skip, held, max_step and theta; ``dscale`` and ``lam`` as
+    it left them, ``step_status`` its status).  ``r_base`` / ``r_probe`` (V, M): the residuals at theta and theta + h delta
+    from one state-only integration, ``status_base`` / ``status_probe`` its statuses.  include/sbm.h says what each tensor
+    holds and what ``accel_status`` means."""
+    V, M, q = J.shape
+    _lib.check(ctx.lib.sbm_lm_geodesic(ctx.handle, p(J), p(r), p(r_base), p(r_probe), p(status_base), p(status_probe), p(dscale),
+                                       p(lam), V, M, q, p(row_scale), p(skip), p(step_status), p(held), float(h), float(alpha),
+                                       float(max_step), p(theta), p(delta), p(trial), p(pred), p(dxnorm), p(gtx),
+                                       p(accel_status), p(ratio), p(n_accel)), 'sbm_lm_geodesic')
 
 
 def mh_propose(ctx, *, curr, samp, z, trial, held=None, lower=None, upper=None, outside=None):

@@ -878,7 +878,9 @@ class Project(object):
         list of ``(p_group, settings)`` pairs.
         ``bounds=``: a box the fitted parameters stay in (log units, like ``thetas0``) -- ``(lower, upper)``, each a scalar,
         (q,) or (V, q), or ``{(p_group, settings): (lo, hi)}``; the result gains 'at_bound' (V, q): -1 / 0 / +1.  Held
-        parameters are exempt; starts must lie inside the box."""
+        parameters are exempt; starts must lie inside the box.
+        ``geodesic=``: ``True`` or ``dict(h=..., alpha=...)`` adds the geodesic acceleration to every step (one more
+        state-only integration of 2 V points per iteration); the result gains 'n_accelerated' (V,).  Not with ``bounds``."""
         from .fitting import levenberg_marquardt_batch
         return levenberg_marquardt_batch(self, thetas0, **options)
 

@@ -14,7 +14,8 @@ from __future__ import annotations
 import numpy as np
 
 from .. import _lib
-from ._evaluation import DeviceEvaluator, finite_cost, inverse_row_sigma, one_device_call, trust_step, usable
+from ._evaluation import (DeviceEvaluator, finite_cost, geodesic_step, inverse_row_sigma, one_device_call, trust_step,
+                          usable)
 
 
 def _trial_budget(project, th, integrator_overrides, n_steps_sum=None, status=None):
@@ -170,6 +171,28 @@ def normalize_bounds(bounds, V, q, project=None, thetas0=None, held=None):
     return lower, upper
 
 
+GEODESIC_H, GEODESIC_ALPHA = 0.1, 0.75          # Transtrum and Sethna's: the probe length and the gate on 2 |a| / |v|
+
+
+def normalize_geodesic(geodesic):
+    """The ``geodesic`` argument of ``fit_batch`` as (h, alpha), or None for the loop without it.  Accepted: None, True
+    (the defaults h = 0.1, alpha = 0.75) or a dict with the keys 'h' and / or 'alpha'.  ValueError on anything else, on
+    h <= 0 and on alpha < 0."""
+    if geodesic is None:
+        return None
+    if geodesic is True:
+        return GEODESIC_H, GEODESIC_ALPHA
+    if not isinstance(geodesic, dict) or set(geodesic) - {'h', 'alpha'}:
+        raise ValueError("geodesic: None, True or a dict with the keys 'h' and 'alpha', not %r" % (geodesic,))
+    try:
+        h, alpha = float(geodesic.get('h', GEODESIC_H)), float(geodesic.get('alpha', GEODESIC_ALPHA))
+    except (TypeError, ValueError):
+        raise ValueError("geodesic: h and alpha are numbers, not %r" % (geodesic,)) from None
+    if not (0.0 < h < float('inf')) or not alpha >= 0.0:
+        raise ValueError("geodesic: h > 0 and alpha >= 0 are needed, got h = %r, alpha = %r" % (h, alpha))
+    return h, alpha
+
+
 def _prepare(project, thetas0, lazy_jacobian):
     """What the three loops below begin with: the refusal of prior rows under ``reference_compat``, ``lazy_jacobian`` resolved,
     the library and the context (device, stream) the project's model lives on, and the starts staged on the device as a copy
@@ -265,6 +288,17 @@ def _median_over(live):
     return lambda t: float(t[live].median()) if some else 0.0
 
 
+def _timed(launch, dev):
+    """``launch()`` between two synchronisations: milliseconds"""
+    import time
+    import torch
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    launch()
+    torch.cuda.synchronize(dev)
+    return 1e3 * (time.perf_counter() - t0)
+
+
 def _traced_launch(integrate_trial, project, ev, tr, done, st, bounded):
     """``trace`` of the fused loop: ``integrate_trial()`` between two synchronisations and the ``launch`` dict of the history entry,
     what the launch cost and why -- it lasts as long as its slowest trajectory (scripts/dev_fit_trace.py).  ``bounded``: ``st``
@@ -306,7 +340,8 @@ def _result(th, cost, n_iter, done, n_eval, n_jac, history=None, held=None, boun
 
 def levenberg_marquardt_batch(project, thetas0, max_iter=60, lambda0=1e-2, lambda_up=4.0, lambda_down=3.0,
                               ftol=1.49012e-8, xtol=1.49012e-8, max_step=2.0, trace=False, lazy_jacobian='auto',
-                              algorithm='trust_region', factor=100.0, held=None, bounds=None, **integrator_overrides):
+                              algorithm='trust_region', factor=100.0, held=None, bounds=None, geodesic=None,
+                              **integrator_overrides):
     """Minimise 0.5 |r(theta)|^2 from every row of ``thetas0`` (V, q), independently.
 
     ``algorithm='trust_region'`` (default since round 2): MINPACK's lmder, batched (`_trust_region_batch` below) -- the
@@ -359,15 +394,33 @@ def levenberg_marquardt_batch(project, thetas0, max_iter=60, lambda0=1e-2, lambd
     pushing outward has converged.  Same support as ``held``; ``bounds=None`` is the loop as it was: the same kernels, the same
     bits.
 
+    ``geodesic``: the geodesic acceleration of every step (Transtrum and Sethna 2012), the remedy for the narrow curved
+    canyons of sloppy models -- ``True``, or ``dict(h=..., alpha=...)`` (defaults 0.1 and 0.75, the paper's).  Per iteration
+    the step v of the trust region is taken as a velocity: theta and theta + h v are integrated WITHOUT sensitivities in one
+    call of 2 V vectors (both ends of the difference from the same kernel: the state-only and the sensitivity kernels differ
+    by the integration tolerance, which a division by h^2 would magnify), ``sbm_lm_geodesic`` forms the second directional
+    derivative r_vv of the residuals, solves the step's own damped system for the acceleration a = -(J^T J + lambda D^2)^-1
+    J^T r_vv and replaces the step by v + a / 2 where 2 ||D a|| <= alpha ||D v|| and the new step still descends in the
+    model; everywhere else the step stays lmder's, and lmder's acceptance logic is unchanged (no step is rejected on the
+    gate).  It is an option and not the default: on Rosenbrock's function it doubles the iterations, and what it buys on
+    the configs[3] project is in docs/history.md.  Supported where ``held`` is, with ``held`` and with ``lazy_jacobian``;
+    not with ``bounds`` (the projection and the active set of an accelerated step are not built).  ``geodesic=None`` is the
+    loop as it was: the same kernels, the same launches, the same bits; ``alpha=0`` pays for the probes and never applies
+    the acceleration.
+
     With a handful of starts the chip is mostly empty: ``variant='small_batch'`` (an integrator override) lets the
     sensitivity kernel use its small-batch split while starts x experiments x chunks <= 2048.
 
     Returns a dict of numpy arrays: theta (V, q), cost (V,) = 0.5 |r|^2, n_iter (V,) iterations until
     convergence (max_iter if never), converged (V,) bool, n_evaluations (total trial points integrated),
     n_jacobian_evaluations (those integrated with sensitivities); with ``held``, 'held' (V, q) bool; with ``bounds``,
-    'at_bound' (V, q) int8: -1 / +1 where the returned theta equals its lower / upper bound, else 0; with
+    'at_bound' (V, q) int8: -1 / +1 where the returned theta equals its lower / upper bound, else 0; with ``geodesic``,
+    'n_accelerated' (V,): the iterations whose step was accelerated (``n_evaluations`` then counts the 2 V probe vectors
+    of every iteration too); with
     ``trace=True`` also 'history': per iteration the number of accepted steps, starts still running, median cost,
-    damping, relative decrease and largest step component (costs a device synchronisation per iteration).
+    damping, relative decrease and largest step component (costs a device synchronisation per iteration); with
+    ``geodesic`` also 'accelerated' (running starts whose step was accelerated), 'rho_median' (2 ||D a|| / ||D v|| over the
+    starts where it was computed; 'rho_p10' and 'rho_p90' beside it) and 'probe_ms' / 'geodesic_ms', the two added launches.
     """
     # the loop's bookkeeping in two device launches per iteration (sbm_lm_update / sbm_lm_accept) whenever the integration is
     # ONE device call; the control loops of _control.py (method='auto', 'implicit_romberg') and algorithm='trust_region_torch'
@@ -378,11 +431,21 @@ def levenberg_marquardt_batch(project, thetas0, max_iter=60, lambda0=1e-2, lambd
                          "that is one device call (not method='auto' / the host-controlled implicit methods); got "
                          "algorithm=%r, method=%r" % ('held parameters' if held is not None else 'bounds', algorithm,
                                                       project._options(**integrator_overrides).get('method')))
+    geodesic = normalize_geodesic(geodesic)
+    if geodesic is not None and not fused:
+        raise ValueError("fit_batch: %s are supported by algorithm='trust_region' with an integration method "
+                         "that is one device call (not method='auto' / the host-controlled implicit methods); got "
+                         "algorithm=%r, method=%r" % ('geodesic steps', algorithm,
+                                                      project._options(**integrator_overrides).get('method')))
+    if geodesic is not None and bounds is not None:
+        raise ValueError("fit_batch: geodesic steps are not supported together with bounds (the projection and the "
+                         "active set of an accelerated step are not built)")
     if algorithm in ('trust_region', 'lmder', 'minpack', 'trust_region_torch'):
         fit = dict(max_iter=max_iter, ftol=ftol, xtol=xtol, factor=factor, trace=trace, lazy_jacobian=lazy_jacobian,
                    max_step=max_step)
         if fused:
-            return _trust_region_fused(project, thetas0, held=held, bounds=bounds, **fit, **integrator_overrides)
+            return _trust_region_fused(project, thetas0, held=held, bounds=bounds, geodesic=geodesic, **fit,
+                                       **integrator_overrides)
         return _trust_region_batch(project, thetas0, **fit, **integrator_overrides)
     if algorithm != 'marquardt':
         raise ValueError("fit_batch: unknown algorithm %r ('marquardt', 'trust_region' or 'trust_region_torch')" % (algorithm,))
@@ -559,7 +622,7 @@ def _trust_region_batch(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
 
 
 def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.49012e-8, factor=100.0, trace=False,
-                        lazy_jacobian='auto', max_step=2.0, held=None, bounds=None, **integrator_overrides):
+                        lazy_jacobian='auto', max_step=2.0, held=None, bounds=None, geodesic=None, **integrator_overrides):
     """`_trust_region_batch` with the bookkeeping on the device: per iteration ONE ``_evaluation.trust_step`` (lmpar, the
     clipped step and the trial point), the integration of the trial points (``sbm_jacobian_batch`` /
     ``sbm_residuals_batch`` into preallocated buffers), ONE ``sbm_lm_update`` (lmder's ratio / radius / acceptance /
@@ -574,7 +637,13 @@ def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
 
     ``bounds``: ``trust_step`` gets the box (``sbm_lm_trust_step_bounded``, with the held mask or NULL), which chooses the active set
     from this iteration's gradient on the device: no read-back is added.  Its status 3 (a constrained stationary point)
-    ends a start in ``sbm_lm_update``; its status 4 (a projected step that does not descend) halves the radius there."""
+    ends a start in ``sbm_lm_update``; its status 4 (a projected step that does not descend) halves the radius there.
+
+    ``geodesic`` = (h, alpha) (`normalize_geodesic`): between ``trust_step`` and the trial integration the 2 V points
+    [theta ; theta + h delta] are written into one preallocated buffer and integrated by ONE state-only call with the
+    trial options and budget, and ``_evaluation.geodesic_step`` (``sbm_lm_geodesic``) replaces delta, trial, pred, dxnorm
+    and gtx of the starts whose acceleration passes the gate.  A copy, an add, the integration and one kernel more, and no
+    read-back: the iteration keeps its one 8-byte read of the counters."""
     import torch
     th, V, q, dev, lib, ctx, lazy_jacobian = _prepare(project, thetas0, lazy_jacobian)
     held_dev = None
@@ -627,14 +696,42 @@ def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
     n_eval, n_jac = V, V
     history = []
     held_i32 = held_dev.to(i32).contiguous() if held_dev is not None else None
+    if geodesic is not None:
+        geo_h, geo_alpha = geodesic
+        points = torch.empty((2 * V, q), dtype=f64, device=dev)         # [theta ; theta + h delta]
+        probe = ev.buffers(2 * V)
+        accel_st = torch.empty((V,), dtype=i32, device=dev)
+        n_accel = torch.zeros((V,), dtype=i32, device=dev)
+        rho = torch.empty((V,), dtype=f64, device=dev) if trace else None
 
     def integrate_trial():
         ev.run(trial, opts_t, tr, not lazy_jacobian)
+
+    def integrate_probe():
+        points[:V].copy_(th)
+        torch.add(th, delta, alpha=geo_h, out=points[V:])
+        ev.run(points, opts_t, probe, False)
+
+    def accelerate():
+        geodesic_step(ctx, J=cur_J, r=cur_r, r_base=probe['residuals'][:V], r_probe=probe['residuals'][V:],
+                      status_base=probe['status'][:V], status_probe=probe['status'][V:], dscale=dscale, lam=lam,
+                      row_scale=row_scale, skip=done, step_status=st, held=held_i32, h=geo_h, alpha=geo_alpha, max_step=max_step,
+                      theta=th, delta=delta, trial=trial, pred=pred, dxnorm=dxnorm, gtx=gtx, accel_status=accel_st, ratio=rho,
+                      n_accel=n_accel)
 
     for it in range(max_iter):
         trust_step(ctx, J=cur_J, r=cur_r, dscale=dscale, radius=radius, lam=lam, row_scale=row_scale, skip=done, max_step=max_step,
                    theta=th, trial=trial, delta=delta, pred=pred, dxnorm=dxnorm, gtx=gtx, status=st, held=held_i32,
                    lower=lower_dev, upper=upper_dev)
+        geo_ms = None
+        if geodesic is not None:
+            if trace:
+                # the two launches between synchronisations of their own, for the history entry
+                geo_ms = (_timed(integrate_probe, dev), _timed(accelerate, dev))
+            else:
+                integrate_probe()
+                accelerate()
+            n_eval += 2 * V
         # the integration of the trial points (launch: the trace's record of it, None without trace)
         launch = _traced_launch(integrate_trial, project, ev, tr, done, st, lower_dev is not None) if trace else integrate_trial()
         n_eval += V
@@ -675,7 +772,18 @@ def _trust_region_fused(project, thetas0, max_iter=60, ftol=1.49012e-8, xtol=1.4
             history.append(dict(iteration=it, accepted=n_acc, live=live, launch=launch, cost_median=float(cost.median()),
                                 lambda_median=md(lam), radius_median=md(radius), ratio_median=md(ratio),
                                 rel_decrease_median=md((cost_prev - cost) / cost_prev)))
+            if geodesic is not None:
+                # (of the starts that were running when the step was made; rho is NaN where it was not computed)
+                was_live = st != 2
+                seen = was_live & ~torch.isnan(rho)
+                lo_q, mid_q, hi_q = (rho[seen].quantile(torch.tensor([0.1, 0.5, 0.9], dtype=f64, device=dev)).tolist()
+                                     if bool(seen.any()) else [float('nan')] * 3)
+                history[-1].update(accelerated=int(((accel_st == 0) & was_live).sum()), rho_median=mid_q, rho_p10=lo_q,
+                                   rho_p90=hi_q, probe_ms=geo_ms[0], geodesic_ms=geo_ms[1])
         if live == 0:
             break
     torch.cuda.synchronize(dev)
-    return _result(th, cost, n_iter, done, n_eval, n_jac, history if trace else None, held, bounds)
+    out = _result(th, cost, n_iter, done, n_eval, n_jac, history if trace else None, held, bounds)
+    if geodesic is not None:
+        out['n_accelerated'] = n_accel.cpu().numpy().astype(np.int64)
+    return out

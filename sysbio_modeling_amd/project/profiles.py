@@ -17,7 +17,7 @@ from .fitting import is_param_pair, param_pair_indices
 
 # what fit_batch itself consumes; everything else in **fit_options is an integrator override (method, rtol, ...)
 _FIT_KEYS = ('max_iter', 'lambda0', 'lambda_up', 'lambda_down', 'ftol', 'xtol', 'max_step', 'trace', 'lazy_jacobian', 'algorithm',
-             'factor', 'bounds')
+             'factor', 'bounds', 'geodesic')
 
 
 def param_indices(project, params, q):
@@ -50,7 +50,8 @@ def profile_likelihood_batch(project, theta_hat, params='all', offsets=np.linspa
     (``fit_batch(held=...)``; ``fit_options`` go there: max_iter, ftol, ..., integrator overrides).  ``bounds=`` among them
     keeps the fitted parameters in a box: a ``(lower, upper)`` pair of scalars or (q,) arrays, or a dict of
     ``(p_group, settings)`` names, the same box for every branch; the profiled parameter, being held, is exempt from it,
-    and ``theta_hat`` has to lie inside.
+    and ``theta_hat`` has to lie inside.  ``geodesic=`` among them (``True`` or ``dict(h=..., alpha=...)``) turns on the
+    geodesic acceleration of every branch's steps, as in ``fit_batch``; together with ``bounds`` it is refused there.
 
     ``continuation=True``: the 2 P branches are the starts of one ``fit_batch`` call per grid step k; a branch starts from
     its own optimum of step k - 1 (``theta_hat`` at k = 0) -- K calls.  ``continuation=False``: all 2 P K points start from
