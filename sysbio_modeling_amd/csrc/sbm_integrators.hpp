@@ -24,6 +24,9 @@
 // The generated model header must define `struct SbmModel` (see
 // sysbio_modeling_amd/symbolic/emit.py::emit_hip) and may use SBM_RCP.
 //
+// Which kernel a call runs, and which instantiations a plugin contains, is said in one place: sbm_kernel_choice.hpp
+// (sbm_choose_kernel, sbm_kernel_built -- plain C++, checked on the host by tests/test_kernel_choice_cpu.py).
+//
 // This file is the umbrella the plugins and tests include; the code is in the headers below, by role, and they are
 // included here only, in this order (none of them stands on its own).
 #pragma once
@@ -51,5 +54,6 @@ struct SbmImplicitFits {
   static constexpr bool adaptive = M::NV <= SBM_IMPLICIT_MAX_NV && sizeof(SbmImadShared<M>) <= 160u * 1024u;
 };
 
-// the host side: which of these kernels a call runs (sbm_launch_model, used by sbm_plugin_main.hip)
+// the host side: sbm_kernel_choice.hpp decides which of these kernels a call runs, sbm_launch_model launches it (used by
+// sbm_plugin_main.hip)
 #include "sbm_launch.hpp"

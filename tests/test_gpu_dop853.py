@@ -60,8 +60,9 @@ def test_cascade20_golden_vectors(gpu_models, golden, zoo):
 
 
 def test_reference_fixture_models(gpu_models, golden):
-    """The reference's own fixtures (1 and 2 states): DOP853 on the row-lane kernel, against the real reference's
-    outputs on its 1000-point grid."""
+    """The reference's own fixtures (1 and 2 states): DOP853 on the packed sensitivity kernel (what AUTO runs for models
+    this small: tests/test_kernel_choice_cpu.py) and the state-rows kernel, against the real reference's outputs on its
+    1000-point grid."""
     for name, fixture in (('simple', 'simple_ref.npz'), ('michaelis_menten', 'mm_ref.npz')):
         m = gpu_models(name)
         g = golden(fixture)

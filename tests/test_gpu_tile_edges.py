@@ -16,7 +16,7 @@ the same check: the bound is one a correct kernel meets.
   bound: 8 x 2.2e-16 = 1.76e-15.  Measured on an MI355X, worst over models, from zero / from given (y0, S0):
     MFMA 4.48e-16 / 3.46e-16, packed 3.95e-16 / 3.46e-16, row-lane 4.22e-16 / 4.45e-16.
 
-A forced variant the launcher does not accept falls back to the row kernels without a word (csrc/sbm_launch.hpp,
+A forced variant the launcher does not accept falls back to the row kernels without a word (csrc/sbm_kernel_choice.hpp,
 row_choice_free): every forced MFMA result here must differ in some bit from the row-lane kernel's and from packed's, and
 under SBM_DEBUG_LAUNCH the launcher must name the forced kernel, with the plan of the CPU table (the packed kernel evaluates
 the row-lane kernel's own FMA chains: its RK4 result is the row-lane kernel's to the bit, so only the launcher can tell).

@@ -2,8 +2,8 @@
 compiles, the structure of those models, and the fixed-step reference the GPU tests compare with.  No GPU needed.
 
 Both kernels choose their lane layout from the model's size at compile time.  The plan is recomputed here in Python from
-the formulas in the comments of csrc/sbm_sens_mfma.hpp (SbmMfmaShared, SbmMfmaPlan) and csrc/sbm_launch.hpp
-(sbm_launch_model), on NV / NK / NNZ_JY read from the generated header, and held against the literal table EXPECTED: the
+the formulas in the comments of csrc/sbm_sens_mfma.hpp (SbmMfmaShared, SbmMfmaPlan) and csrc/sbm_kernel_choice.hpp
+(sbm_choose_kernel), on NV / NK / NNZ_JY read from the generated header, and held against the literal table EXPECTED: the
 evidence of which instantiation each test of tests/test_gpu_tile_edges.py addresses.
 
   MFMA     RT = ceil(NV / 16) row tiles, CT = min(ceil(NK / 16), max(1, 12 / (4 RT))) column tiles per wavefront,
