@@ -600,6 +600,38 @@ int sbm_mh_accept_ex(sbm_ctx* ctx, const double* norms_trial_dev, const int32_t*
                      const double* trial_dev, double* curr_dev, double* F_curr_dev, int32_t* n_accepted_dev,
                      double* ens_slot_dev, double* ens_F_slot_dev, const int32_t* veto_dev);
 
+/* ---- parallel tempering (project/ensembles.py, `temperature=` a ladder, `swap_every=`) ---- */
+/* The C chains are C / K ladders of K rungs: chain c is rung c % K of ladder c / K and keeps its temperature for the whole
+ * run; a replica exchange moves the points.  The three entries below are added exports: SBM_ABI_VERSION is unchanged.
+ *
+ * sbm_project_sf_entropy with the temperature of vector v read from temperature[v] ([V], device): the same kernel body, so
+ * with all entries equal to T the bits of sbm_project_sf_entropy(..., T, ...).  An entry that is not positive and finite
+ * gives entropy[v] = -inf and group_entropy[v][:] = -inf. */
+int sbm_project_sf_entropy_pt(sbm_project* project, const double* sims_dev, int32_t V, const double* temperature_dev,
+                              double* entropy_dev, double* group_entropy_dev);
+
+/* sbm_mh_accept_ex with the temperature of chain c read from temperature[c] ([C], device): log_u[c] < -(F_trial[c] -
+ * F_curr[c]) / temperature[c].  With all entries equal to T the bits of sbm_mh_accept_ex.  A chain whose temperature is not
+ * positive and finite stays. */
+int sbm_mh_accept_pt(sbm_ctx* ctx, const double* norms_trial_dev, const int32_t* status_trial_dev,
+                     const double* entropy_trial_dev, const double* log_u_dev, const double* temperature_dev, int32_t C,
+                     int32_t q, const double* trial_dev, double* curr_dev, double* F_curr_dev, int32_t* n_accepted_dev,
+                     double* ens_slot_dev, double* ens_F_slot_dev, const int32_t* veto_dev);
+
+/* One replica-exchange step.  In every ladder it proposes the pairs of rungs (k, k + 1) with k % 2 == parity and k + 1 < K.
+ * With i the lower chain of a pair, j = i + 1, and F_cross[c] the energy of chain c's point at its partner's temperature
+ * (NULL: F_curr stands in -- an energy that does not depend on the temperature), the two points are exchanged iff F_cross[i]
+ * and F_cross[j] are finite and
+ *     log_u[i] < (F_curr[i] - F_cross[j]) / T[i] + (F_curr[j] - F_cross[i]) / T[j],
+ * evaluated in this order.  An exchange swaps rows i and j of curr [C][q], sets F_curr[i] = F_cross[j] and F_curr[j] =
+ * F_cross[i], adds 1 to n_swapped[i] (the lower chain counts) and, where ens_slot [C][q] / ens_F_slot [C] are given (a kept
+ * step: the slots sbm_mh_accept* has just written), rewrites their two rows.  Everything else -- the chains outside a pair, a
+ * pair that is not exchanged, log_u of the other chains -- is neither written nor looked at: it keeps every bit.
+ * One wavefront per chain, no LDS.  SBM_E_ARG for C % K != 0, K < 2, parity outside {0, 1} or a NULL required pointer. */
+int sbm_pt_swap(sbm_ctx* ctx, int32_t C, int32_t q, int32_t K, int32_t parity, const double* temperature_dev,
+                const double* F_cross_dev, const double* log_u_dev, double* curr_dev, double* F_curr_dev,
+                int32_t* n_swapped_dev, double* ens_slot_dev, double* ens_F_slot_dev);
+
 /* ---- the sampler's second algorithm (project/ensembles.py, sampler='device_recalc') ---- */
 /* Axes of the Gaussian candidate density from a Hessian per chain (the reference's _sampling_matrix, Ensembles.py:226-258,
  * SloppyCell's recipe), for C chains in one launch.  Exactly one of J and H is non-NULL:

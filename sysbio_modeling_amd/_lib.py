@@ -112,6 +112,9 @@ SIGNATURES = {
     'sbm_mh_accept': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sbm_mh_propose_box': (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     'sbm_mh_accept_ex': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sbm_project_sf_entropy_pt': (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    'sbm_mh_accept_pt': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sbm_pt_swap': (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sbm_sampling_axes_held': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.c_double, ctypes.c_double,
                                               ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     'sbm_mh_accept_hastings_ex': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -14,7 +14,7 @@
 //                           step, lmder's trust-region step and bookkeeping)
 //   sbm_lm_geodesic.hpp     k_lm_geodesic: the second-order (geodesic) correction of the trust-region step, on sbm_lm.hpp's
 //                           builder of the normal equations and its factorisation
-//   sbm_sampler.hpp         k_sf_entropy, k_mh_propose[_box], k_mh_accept, k_mh_accept_hastings: scale-factor entropy integrals
+//   sbm_sampler.hpp         k_sf_entropy[_pt], k_mh_propose[_box], k_mh_accept[_pt], k_mh_accept_hastings, k_pt_swap: scale-factor entropy integrals
 //                           (linear_scale_factor.py:63-81; the quadrature rule: sbm_sf_quadrature.hpp), candidate move and
 //                           the two acceptance rules of the multi-chain sampler (project/Ensembles.py:193-198, 200-264)
 //   sbm_sampling_axes.hpp   k_sampling_axes[_held]: per-chain Hessian axes (batched Jacobi eigensolver + SloppyCell's clipping
@@ -998,6 +998,19 @@ extern "C" int sbm_project_sf_entropy(sbm_project* p, const double* sims, int32_
                     p->row_sigma.p, p->row_sf.p, p->sfg_mean.p, p->sfg_sigma.p, temperature, entropy, group_entropy);
 }
 
+extern "C" int sbm_project_sf_entropy_pt(sbm_project* p, const double* sims, int32_t V, const double* temperature, double* entropy,
+                                         double* group_entropy) {
+  if (!p || !sims || !temperature || !entropy) return sbm_fail(SBM_E_ARG, "sbm_project_sf_entropy_pt: NULL argument");
+  if (V < 0) return sbm_fail(SBM_E_ARG, "sbm_project_sf_entropy_pt: V < 0");
+  if (p->G <= 0) return sbm_fail(SBM_E_ARG, "sbm_project_sf_entropy_pt: the project has no scale factors");
+  if (p->sf_group_without_prior >= 0)
+    return sbm_fail(SBM_E_ARG, "sbm_project_sf_entropy_pt: scale factor entropy needs a log prior on every scale factor (group %d has none)",
+                    p->sf_group_without_prior);
+  if (V == 0) return 0;
+  return launch_lds(p->model->ctx, k_sf_entropy_pt, dim3(V), dim3(256), sizeof(double) * (size_t)p->G, sims, p->R, p->G, p->row_data.p,
+                    p->row_sigma.p, p->row_sf.p, p->sfg_mean.p, p->sfg_sigma.p, temperature, entropy, group_entropy);
+}
+
 extern "C" int sbm_mh_propose(sbm_ctx* ctx, const double* curr, const double* samp, int32_t per_chain, const double* z, int32_t C,
                               int32_t q, double* trial) {
   if (!ctx || !curr || !samp || !z || !trial) return sbm_fail(SBM_E_ARG, "sbm_mh_propose: NULL argument");
@@ -1037,6 +1050,35 @@ extern "C" int sbm_mh_accept_ex(sbm_ctx* ctx, const double* norms_trial, const i
                 veto};
   SBM_HIP(hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_mh_accept, dim3((C + 3) / 4), dim3(256), 0, ctx->stream, a);
+  SBM_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int sbm_mh_accept_pt(sbm_ctx* ctx, const double* norms_trial, const int32_t* status_trial, const double* entropy_trial,
+                                const double* log_u, const double* temperature, int32_t C, int32_t q, const double* trial, double* curr,
+                                double* F_curr, int32_t* n_accepted, double* ens_slot, double* ens_F_slot, const int32_t* veto) {
+  if (!ctx || !norms_trial || !status_trial || !log_u || !temperature || !trial || !curr || !F_curr || !n_accepted)
+    return sbm_fail(SBM_E_ARG, "sbm_mh_accept_pt: NULL argument");
+  if (C < 0 || q <= 0) return sbm_fail(SBM_E_ARG, "sbm_mh_accept_pt: bad sizes C=%d q=%d", C, q);
+  if (C == 0) return 0;
+  sbm_mh_args a{norms_trial, status_trial, entropy_trial, log_u, 0.0, C, q, trial, curr, F_curr, n_accepted, ens_slot, ens_F_slot, veto};
+  SBM_HIP(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(k_mh_accept_pt, dim3((C + 3) / 4), dim3(256), 0, ctx->stream, a, temperature);
+  SBM_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int sbm_pt_swap(sbm_ctx* ctx, int32_t C, int32_t q, int32_t K, int32_t parity, const double* temperature,
+                           const double* F_cross, const double* log_u, double* curr, double* F_curr, int32_t* n_swapped,
+                           double* ens_slot, double* ens_F_slot) {
+  if (!ctx || !temperature || !log_u || !curr || !F_curr || !n_swapped) return sbm_fail(SBM_E_ARG, "sbm_pt_swap: NULL argument");
+  if (C < 0 || q <= 0) return sbm_fail(SBM_E_ARG, "sbm_pt_swap: bad sizes C=%d q=%d", C, q);
+  if (K < 2 || C % K != 0) return sbm_fail(SBM_E_ARG, "sbm_pt_swap: C=%d chains are not ladders of K=%d >= 2 rungs", C, K);
+  if (parity != 0 && parity != 1) return sbm_fail(SBM_E_ARG, "sbm_pt_swap: parity %d is neither 0 nor 1", parity);
+  if (C == 0) return 0;
+  sbm_pt_swap_args a{C, q, K, parity, temperature, F_cross, log_u, curr, F_curr, n_swapped, ens_slot, ens_F_slot};
+  SBM_HIP(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(k_pt_swap, dim3((C + 3) / 4), dim3(256), 0, ctx->stream, a);
   SBM_HIP(hipGetLastError());
   return 0;
 }

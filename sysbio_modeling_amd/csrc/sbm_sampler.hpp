@@ -2,7 +2,9 @@
 // 'device_recalc'): scale-factor entropy of the trial simulations (sbm_project_sf_entropy; the quadrature rule itself is
 // sbm_sf_quadrature.hpp, which is also compiled for the host), candidate move (sbm_mh_propose; inside a box and with held
 // components: sbm_mh_propose_box), and the two acceptance rules (sbm_mh_accept[_ex], sbm_mh_accept_hastings[_ex]).  Between sbm_mh_propose, sbm_residuals_batch, sbm_project_sf_entropy
-// and the acceptance no number goes through the host.  The host wrappers with the argument checks are in sbm_core.hip.
+// and the acceptance no number goes through the host.  Parallel tempering adds one temperature per vector / chain to the
+// entropy and to the Metropolis rule (sbm_project_sf_entropy_pt, sbm_mh_accept_pt: the same bodies, the temperature read
+// from an array) and the replica-exchange step (sbm_pt_swap).  The host wrappers with the argument checks are in sbm_core.hip.
 #ifndef SBM_SAMPLER_HPP
 #define SBM_SAMPLER_HPP
 
@@ -17,13 +19,30 @@
 // (sbm_sf_quadrature.hpp) do: lane l integrates panels l and l + 64 and the wavefront combines the 64 partial
 // log-sum-exps.  LDS: the G group values of the vector, summed in group order by one thread, so that the entropy does
 // not depend on which wavefront finished first.
-__global__ void __launch_bounds__(256) k_sf_entropy(const double* __restrict__ sims, int R, int G,
-                                                    const double* __restrict__ row_data, const double* __restrict__ row_sigma,
-                                                    const int32_t* __restrict__ row_sf, const double* __restrict__ sfg_mean,
-                                                    const double* __restrict__ sfg_sigma, double temperature,
-                                                    double* __restrict__ entropy, double* __restrict__ group_entropy) {
-  extern __shared__ double s_group[];   // [G]
+//
+// Where the temperature of vector v comes from: one number for the launch (sbm_project_sf_entropy, whose wrapper has
+// checked it) or one per vector (sbm_project_sf_entropy_pt: the rungs of a temperature ladder; an entry that is not
+// positive gives the vector the entropy -inf, as a simulation that is not finite does).  The body below is written once.
+struct sf_temperature_one {
+  double T;
+  __device__ __forceinline__ double of(int) const { return T; }
+  __device__ __forceinline__ bool usable(double) const { return true; }
+};
+struct sf_temperature_each {
+  const double* T;   // [V]
+  __device__ __forceinline__ double of(int v) const { return T[v]; }
+  __device__ __forceinline__ bool usable(double t) const { return t > 0.0 && is_finite(t); }
+};
+
+template <class Temperature>
+__device__ __forceinline__ void sf_entropy_vector(const double* __restrict__ sims, int R, int G, const double* __restrict__ row_data,
+                                                  const double* __restrict__ row_sigma, const int32_t* __restrict__ row_sf,
+                                                  const double* __restrict__ sfg_mean, const double* __restrict__ sfg_sigma,
+                                                  Temperature from, double* __restrict__ entropy, double* __restrict__ group_entropy,
+                                                  double* s_group /* LDS [G] */) {
   const int v = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const double temperature = from.of(v);
+  const bool t_ok = from.usable(temperature);
   const double* sv = sims + (size_t)v * R;
   for (int k = wave; k < G; k += 4) {
     double a = 0.0, b = 0.0;
@@ -41,7 +60,7 @@ __global__ void __launch_bounds__(256) k_sf_entropy(const double* __restrict__ s
     b = wave_sum(b);
     bad = __any(bad);
     double alpha = 0.0, c = 0.0, val = -__builtin_inf();
-    if (!bad && sbm_sfq_params(a, b, sfg_mean[k], temperature, &alpha, &c)) {
+    if (!bad && t_ok && sbm_sfq_params(a, b, sfg_mean[k], temperature, &alpha, &c)) {
       sbm_sfq_plan q;
       sbm_sfq_make_plan(alpha, c, sfg_sigma[k], &q);         // (the same on every lane)
       double m = -__builtin_inf(), sum = 0.0;
@@ -60,8 +79,29 @@ __global__ void __launch_bounds__(256) k_sf_entropy(const double* __restrict__ s
   if (threadIdx.x == 0) {
     double e = 0.0;
     for (int k = 0; k < G; ++k) e += temperature * s_group[k];
-    entropy[v] = e == e ? e : -__builtin_inf();
+    entropy[v] = (t_ok && e == e) ? e : -__builtin_inf();
   }
+}
+
+__global__ void __launch_bounds__(256) k_sf_entropy(const double* __restrict__ sims, int R, int G,
+                                                    const double* __restrict__ row_data, const double* __restrict__ row_sigma,
+                                                    const int32_t* __restrict__ row_sf, const double* __restrict__ sfg_mean,
+                                                    const double* __restrict__ sfg_sigma, double temperature,
+                                                    double* __restrict__ entropy, double* __restrict__ group_entropy) {
+  extern __shared__ double s_group[];   // [G]
+  sf_entropy_vector(sims, R, G, row_data, row_sigma, row_sf, sfg_mean, sfg_sigma, sf_temperature_one{temperature}, entropy,
+                    group_entropy, s_group);
+}
+
+// The same with the temperature of vector v read from temperature[v] (sbm_project_sf_entropy_pt)
+__global__ void __launch_bounds__(256) k_sf_entropy_pt(const double* __restrict__ sims, int R, int G,
+                                                       const double* __restrict__ row_data, const double* __restrict__ row_sigma,
+                                                       const int32_t* __restrict__ row_sf, const double* __restrict__ sfg_mean,
+                                                       const double* __restrict__ sfg_sigma, const double* __restrict__ temperature,
+                                                       double* __restrict__ entropy, double* __restrict__ group_entropy) {
+  extern __shared__ double s_group[];   // [G]
+  sf_entropy_vector(sims, R, G, row_data, row_sigma, row_sf, sfg_mean, sfg_sigma, sf_temperature_each{temperature}, entropy,
+                    group_entropy, s_group);
 }
 
 // trial = curr + samp z: one thread per (chain, component); samp is one [q][q] matrix or one per chain
@@ -154,14 +194,78 @@ __device__ __forceinline__ void mh_commit(const sbm_mh_args& a, int c, bool acc,
   }
 }
 
+// The Metropolis rule of chain c at the temperature T, by the 64 lanes of its wavefront
+__device__ __forceinline__ void mh_metropolis(const sbm_mh_args& a, int c, double T, int lane) {
+  const double Fc = a.F_curr[c];
+  double Ft;
+  const bool acc = mh_trial_energy(a, c, &Ft) && a.log_u[c] < -(Ft - Fc) / T;
+  mh_commit(a, c, acc, Ft, Fc, lane, 64);
+}
+
 // The Metropolis rule.  One wavefront per chain: every lane reads the chain's scalars and takes the same decision.
 __global__ void __launch_bounds__(256) k_mh_accept(sbm_mh_args a) {
   const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (c >= a.C) return;
-  const double Fc = a.F_curr[c];
-  double Ft;
-  const bool acc = mh_trial_energy(a, c, &Ft) && a.log_u[c] < -(Ft - Fc) / a.temperature;
-  mh_commit(a, c, acc, Ft, Fc, lane, 64);
+  mh_metropolis(a, c, a.temperature, lane);
+}
+
+// The same with one temperature per chain (sbm_mh_accept_pt; a.temperature is not read).  A device array cannot be checked
+// by the wrapper, so the kernel does: a chain whose temperature is not positive and finite stays.
+__global__ void __launch_bounds__(256) k_mh_accept_pt(sbm_mh_args a, const double* __restrict__ temperature) {
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (c >= a.C) return;
+  const double T = temperature[c];
+  // (a NaN bound compares false: the chain stays and the record slots still get its point)
+  mh_metropolis(a, c, T > 0.0 && is_finite(T) ? T : __builtin_nan(""), lane);
+}
+
+// One replica-exchange step of the temperature ladders (sbm_pt_swap; project/ensembles.py, `temperature=` a ladder with
+// `swap_every=`).  The C chains are C / K ladders of K contiguous rungs; this step proposes the pairs (k, k + 1) with
+// k % 2 == parity.  The launch shape of k_mh_accept: one wavefront per chain, four per workgroup.  The wavefront of a
+// pair's lower chain i decides from the scalars -- every lane the same way -- and then exchanges the rows i and j = i + 1
+// with its lanes striding over q; every other wavefront returns.  Pairs are disjoint, so no two wavefronts touch the same
+// row, and a chain outside an exchanged pair keeps every bit (the rows move as they are: no arithmetic on them).
+struct sbm_pt_swap_args {
+  int C, q, K, parity;
+  const double* temperature;   // [C]
+  const double* F_cross;       // [C] nullable: the energy of chain c's point at its partner's temperature; NULL = F_curr
+  const double* log_u;         // [C] read at the lower chain of a pair
+  double* curr;                // [C][q]    in / out
+  double* F_curr;              // [C]       in / out
+  int32_t* n_swapped;          // [C]       in / out, counted at the lower chain
+  double* ens_slot;            // [C][q]    nullable
+  double* ens_F_slot;          // [C]       nullable
+};
+
+__global__ void __launch_bounds__(256) k_pt_swap(sbm_pt_swap_args a) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= a.C) return;
+  const int k = i % a.K;
+  if ((k & 1) != a.parity || k + 1 >= a.K) return;      // not the lower chain of a pair of this step
+  const int j = i + 1;                                   // the same ladder: k + 1 < K and C % K == 0, so j < C
+  const double Fi = a.F_curr[i], Fj = a.F_curr[j];
+  const double Xi = a.F_cross ? a.F_cross[i] : Fi, Xj = a.F_cross ? a.F_cross[j] : Fj;
+  const double bound = (Fi - Xj) / a.temperature[i] + (Fj - Xi) / a.temperature[j];
+  if (!(is_finite(Xi) && is_finite(Xj) && a.log_u[i] < bound)) return;
+  const size_t oi = (size_t)i * a.q, oj = (size_t)j * a.q;
+  for (int e = lane; e < a.q; e += 64) {
+    const double xi = a.curr[oi + e], xj = a.curr[oj + e];
+    a.curr[oi + e] = xj;
+    a.curr[oj + e] = xi;
+    if (a.ens_slot) {
+      a.ens_slot[oi + e] = xj;
+      a.ens_slot[oj + e] = xi;
+    }
+  }
+  if (lane == 0) {
+    a.F_curr[i] = Xj;
+    a.F_curr[j] = Xi;
+    a.n_swapped[i] += 1;
+    if (a.ens_F_slot) {
+      a.ens_F_slot[i] = Xj;
+      a.ens_F_slot[j] = Xi;
+    }
+  }
 }
 
 struct sbm_mh_hastings_args {

@@ -1,7 +1,7 @@
 """What every host loop around the project kernels shares (project/fitting.py, project/ensembles.py, base_project.py): the
 one place that calls ``sbm_residuals_batch`` / ``sbm_jacobian_batch``, the output set those calls fill, the three small
 rules the loops apply to what comes back, and the other per-step device calls of the loops (``trust_step``, ``geodesic_step``, ``mh_propose``,
-``mh_accept``, ``sampling_axes``), each written once.  torch is imported inside the functions: it loads without a GPU."""
+``mh_accept``, ``pt_swap``, ``sampling_axes``), each written once.  torch is imported inside the functions: it loads without a GPU."""
 from __future__ import annotations
 
 import ctypes
@@ -143,8 +143,18 @@ def mh_accept(ctx, *, norms, status, log_u, temperature, trial, curr, F_curr, n_
     """Accept or reject the C trial points and move ``curr`` / ``F_curr`` / ``n_accepted`` (and the record slots, when
     given): ``sbm_mh_accept_ex``, or with ``axes_curr`` / ``axes_trial`` = (V, s, samp) of the candidate density at the two
     ends and the trial axes' ``axes_status`` ``sbm_mh_accept_hastings_ex``, which moves the axes with the point.  ``veto``
-    int32 (C,) or NULL: the unsuffixed entry points are these with NULL."""
+    int32 (C,) or NULL: the unsuffixed entry points are these with NULL.  ``temperature``: a number, or a float64 device
+    tensor (C,) with one temperature per chain -- ``sbm_mh_accept_pt``, the Metropolis rule only."""
     C, q = curr.shape
+    if hasattr(temperature, 'data_ptr'):
+        if axes_curr is not None:
+            raise ValueError("mh_accept: one temperature per chain goes with the Metropolis rule, not with axes")
+        if tuple(temperature.shape) != (C,):
+            raise ValueError("mh_accept: temperature must be a number or have shape (%d,), not %s" % (C, tuple(temperature.shape)))
+        _lib.check(ctx.lib.sbm_mh_accept_pt(ctx.handle, p(norms), p(status), p(entropy), p(log_u), p(temperature), C, q, p(trial),
+                                            p(curr), p(F_curr), p(n_accepted), p(ens_slot), p(ens_F_slot), p(veto)),
+                   'sbm_mh_accept_pt')
+        return
     args = (ctx.handle, p(norms), p(status), p(entropy), p(log_u), float(temperature), C, q, p(trial), p(curr), p(F_curr),
             p(n_accepted), p(ens_slot), p(ens_F_slot))
     if axes_curr is not None:
@@ -152,6 +162,16 @@ def mh_accept(ctx, *, norms, status, log_u, temperature, trial, curr, F_curr, n_
                                                      p(axes_status), p(veto)), 'sbm_mh_accept_hastings_ex')
     else:
         _lib.check(ctx.lib.sbm_mh_accept_ex(*args, p(veto)), 'sbm_mh_accept_ex')
+
+
+def pt_swap(ctx, *, K, parity, temperature, log_u, curr, F_curr, n_swapped, F_cross=None, ens_slot=None, ens_F_slot=None):
+    """``sbm_pt_swap``: one replica-exchange step of the C / K temperature ladders in ``curr`` (C, q) -- the pairs of rungs
+    (k, k + 1) with k % 2 == ``parity``.  ``temperature`` (C,) the chains' own, ``F_cross`` (C,) the energies of their points
+    at the partners' temperatures (None: ``F_curr``), ``log_u`` (C,) read at the lower chain of a pair, ``n_swapped`` int32
+    (C,) counted there; the record slots of a kept step, when given, get the exchanged rows."""
+    C, q = curr.shape
+    _lib.check(ctx.lib.sbm_pt_swap(ctx.handle, C, q, int(K), int(parity), p(temperature), p(F_cross), p(log_u), p(curr), p(F_curr),
+                                   p(n_swapped), p(ens_slot), p(ens_F_slot)), 'sbm_pt_swap')
 
 
 def sampling_axes(ctx, *, status, cutoff, temperature, step_scale, J=None, row_scale=None, H=None, eig=None, V=None, s=None,

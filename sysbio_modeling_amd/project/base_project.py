@@ -831,7 +831,9 @@ class Project(object):
         a log-sum-exp (csrc/sbm_sf_quadrature.hpp).  ``sims`` (V, n_project_residuals), numpy or torch CUDA; the result
         (V,) is of the same kind, and with ``group_entropy=True`` a pair with the (V, G) log-integrals.  -inf where a
         simulation is not finite or a group's best-fit scale factor is not positive (the host method gives NaN there).
-        Every group needs a log prior: ValueError otherwise, as from the host method."""
+        Every group needs a log prior: ValueError otherwise, as from the host method.
+        ``temperature``: a number, or (V,) one per vector, numpy or torch (``sbm_project_sf_entropy_pt``: the same kernel
+        body, the bits of the scalar entry where the temperatures are equal)."""
         import torch
         self._require_scale_factor_priors()
         proj = self._device()
@@ -847,8 +849,16 @@ class Project(object):
         V, G = sd.shape[0], self._n_sf_groups()
         ent = torch.empty((V,), dtype=torch.float64, device=dev)
         grp = torch.empty((V, G), dtype=torch.float64, device=dev) if group_entropy else None
-        _lib.check(_lib.load_library().sbm_project_sf_entropy(proj, _lib.dev_ptr(sd), V, float(temperature), _lib.dev_ptr(ent),
-                                                              _lib.dev_ptr(grp)), 'sbm_project_sf_entropy')
+        if np.ndim(temperature) == 0:
+            _lib.check(_lib.load_library().sbm_project_sf_entropy(proj, _lib.dev_ptr(sd), V, float(temperature), _lib.dev_ptr(ent),
+                                                                  _lib.dev_ptr(grp)), 'sbm_project_sf_entropy')
+        else:
+            td = temperature if isinstance(temperature, torch.Tensor) else torch.from_numpy(_as_f64(temperature))
+            td = td.to(device=dev, dtype=torch.float64).contiguous()
+            if tuple(td.shape) != (V,):
+                raise ValueError("temperature must be a number or have shape (%d,), not %s" % (V, tuple(td.shape)))
+            _lib.check(_lib.load_library().sbm_project_sf_entropy_pt(proj, _lib.dev_ptr(sd), V, _lib.dev_ptr(td), _lib.dev_ptr(ent),
+                                                                     _lib.dev_ptr(grp)), 'sbm_project_sf_entropy_pt')
         if not as_torch:
             torch.cuda.synchronize(dev)
             ent = ent.cpu().numpy()
@@ -858,7 +868,8 @@ class Project(object):
     def free_energy_batch(self, thetas, temperature=1, device=False, **integrator_overrides):
         """free_energy for V parameter vectors: one batched device evaluation, then the quadratures -- on the host, one
         ``scipy.integrate.quad`` per vector and group (``device=False``, the default), or on the device
-        (``device=True``: ``scale_factors_entropy_batch``; +inf where that gives -inf)."""
+        (``device=True``: ``scale_factors_entropy_batch``; +inf where that gives -inf).  ``temperature``: a number, or (V,)
+        one per vector -- F(theta_v; T_v), the energies of the rungs of a temperature ladder."""
         if device:
             th, as_torch = self._theta_dev(thetas)
             res = self.evaluate_batch(th, want=('sims', 'norms', 'status'), **integrator_overrides)
@@ -866,8 +877,13 @@ class Project(object):
             return out if as_torch else out.cpu().numpy()
         res = self.evaluate_batch(thetas, **integrator_overrides)
         out = 0.5 * res['norms']
+        if np.ndim(temperature) != 0:
+            temperature = np.asarray(temperature.cpu() if hasattr(temperature, 'cpu') else temperature, dtype=float)
+            if temperature.shape != out.shape:
+                raise ValueError("temperature must be a number or have shape %s, not %s" % (out.shape, temperature.shape))
         for v in range(len(out)):
-            out[v] = out[v] - self.calc_scale_factors_entropy(temperature, sims=res['sims'][v]) \
+            T = temperature if np.ndim(temperature) == 0 else temperature[v]
+            out[v] = out[v] - self.calc_scale_factors_entropy(T, sims=res['sims'][v]) \
                 if np.isfinite(out[v]) else np.inf
         return out
 

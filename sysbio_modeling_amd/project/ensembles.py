@@ -22,7 +22,7 @@ import numpy as np
 
 from .. import _lib
 from ._evaluation import (DeviceEvaluator, finite_cost, inverse_row_sigma, mh_accept, mh_propose, one_device_call,
-                          sampling_axes as device_sampling_axes)
+                          pt_swap, sampling_axes as device_sampling_axes)
 from .chain_diagnostics import (DEFAULT_MAX_LAG, _chain_steps, _ensemble_diagnostics_dev, autocorrelation,  # noqa: F401
                                 ensemble_diagnostics)
 from .predictions import (DEFAULT_QUANTILES, EnsembleTrajectories, _experiment_measures, ensemble_predictions,  # noqa: F401
@@ -108,12 +108,36 @@ def _log_candidate_density(step, V, s):
     return -0.5 * np.sum(u * u, axis=1) - np.sum(np.log(s), axis=1)
 
 
+def temperature_ladder(K, t_max):
+    """The geometric temperature ladder of K rungs from 1 to ``t_max``, ``np.geomspace(1, t_max, K)``: equal ratios between
+    neighbours, which gives equal swap rates between them where the heat capacity is constant (a Gaussian posterior)."""
+    return np.geomspace(1.0, float(t_max), int(K))
+
+
 def ensemble_log_params_batch(project, params, hess=None, steps=1000, temperature=1.0, step_scale=1.0,
                               sing_val_cutoff=0.0, seeds=None, skip_elems=0, energy='auto', recalc_hess_alg=False,
-                              sampler='host', draws=None, held=None, bounds=None, diagnostics=False, **integrator_overrides):
+                              sampler='host', draws=None, held=None, bounds=None, diagnostics=False, swap_every=None,
+                              **integrator_overrides):
     """C Metropolis chains in log-parameter space, advanced together.
 
     params : (q,) start shared by all chains, or (C, q) one start per chain (``n_chains`` = C).
+    temperature : a number -- every chain samples exp(-F / T) --, or a ladder (T_0, ..., T_{K-1}) of K >= 2 positive
+             temperatures, in any order, for parallel tempering (replica exchange): C must be a multiple of K, chain c
+             is rung c % K of ladder c // K (the rungs of a ladder are neighbours) and samples exp(-F(theta; T_k) / T_k) for
+             the whole run, with its own candidate density ``sampling_matrix(hess, cutoff, T_k, step_scale)``.  So
+             ``ens[:, c]`` is a sample at T[c % K] and ``ens[:, ::K]`` are the chains of rung 0; ``ens_Fs[:, c]`` holds
+             F(x_c; T_c).  The first algorithm only, with ``sampler='host'`` or ``'device'``.
+    swap_every : with a ladder, a replica-exchange step after the acceptance of every ``swap_every``-th step.  The n-th of
+             them (from 0) proposes, in every ladder, the pairs of rungs (k, k + 1) with k % 2 == n % 2; with i the lower
+             chain, j = i + 1 and F_cross[c] = F(x_c; T of c's partner) the two chains exchange their POINTS -- a chain
+             keeps its temperature -- iff both cross energies are finite and
+             log u < (F[i] - F_cross[j]) / T[i] + (F[j] - F_cross[i]) / T[j]  (for 'rss', whose energy does not depend on T:
+             (F_i - F_j) (1 / T_i - 1 / T_j)).  With 'free_energy' a swap step evaluates the current points once more
+             (state only) for the cross energies; on the device that is one ``sbm_residuals_batch``, one
+             ``sbm_project_sf_entropy_pt`` and one ``sbm_pt_swap``, still without a read-back.  Whole rows are exchanged, so
+             ``held`` masks, the start values of held columns and ``bounds`` must be equal within a ladder (ValueError).
+             None with a ladder is legal: independent chains at different temperatures.  With a scalar temperature it must
+             be None (ValueError), and every sampler then enqueues the kernels it enqueued before ladders existed.
     hess   : (q, q) Hessian for the candidate density (default: J^T J at the first start).
     recalc_hess_alg : the reference's second algorithm (Ensembles.py:153-157, 200-224): every chain draws its
              candidate from the Gauss-Newton Hessian J^T J AT ITS CURRENT POINT and the move is accepted with the
@@ -140,7 +164,10 @@ def ensemble_log_params_batch(project, params, hess=None, steps=1000, temperatur
              parameters.
     draws : (z, log_u) of shapes (steps, C, q) and (steps, C): the standard normal and log-uniform numbers to use
              instead of drawing them (the two device samplers only).  With 'device_recalc' the move is V (s z) with the
-             eigenvectors signed as ``sbm_sampling_axes`` signs them (include/sbm.h).
+             eigenvectors signed as ``sbm_sampling_axes`` signs them (include/sbm.h).  With ``swap_every`` a third array is
+             required, (z, log_u, log_u_swap): log_u_swap (steps // swap_every, C), of which a swap step reads the entry of
+             each pair's lower chain.  Without ``draws`` the swap numbers come from a second generator derived from
+             ``seeds``; the two existing streams deliver the numbers they delivered before.
     held   : parameters that never move, in the forms of ``fit_batch(held=)`` (``fitting.normalize_held``: a bool mask (q,)
              or (C, q) -- masks may differ from chain to chain --, indices, or (p_group, settings) pairs): every kept point has
              the start's value there.  The candidate density lives in the free subspace (``sampling_axes(held=)``: the recipe
@@ -157,20 +184,26 @@ def ensemble_log_params_batch(project, params, hess=None, steps=1000, temperatur
              With both None every sampler launches the kernels it launched before these arguments existed: the same bits.
     diagnostics : True adds a fourth element, the dict of ``ensemble_diagnostics(ens, ens_Fs)`` (default lag window, no
              thinning).  The device samplers compute it from the record on the device, before the read-back they end with;
-             ``sampler='host'`` uploads its record.  False (default): today's 3-tuple through today's calls.
+             ``sampler='host'`` uploads its record.  False (default): today's 3-tuple through today's calls.  With a ladder
+             the diagnostics cover the chains of rung 0 only, through a contiguous copy of ``ens[:, ::K]`` (C / K chains):
+             R-hat across chains that sample different temperatures means nothing.
     Returns (ens, ens_Fs, ratio): ens (n_kept, C, q) parameter sets including the starts, ens_Fs
-    (n_kept, C) their energies, ratio (C,) accepted / attempted per chain.
+    (n_kept, C) their energies, ratio (C,) accepted / attempted per chain.  With a ladder one more element comes last, the
+    dict temperature (C,), rung (C,), ladder (C,), swap_attempted (C,), swap_accepted (C,) -- the last two counted at the
+    lower chain of each pair (0 at the top rung): swap_accepted / swap_attempted of chain c is the swap ratio between the
+    rungs c % K and c % K + 1 of its ladder.
     """
     starts = np.atleast_2d(np.asarray(params, dtype=float))
     C, q = starts.shape
     _check_sampler_arguments(sampler, recalc_hess_alg, draws, diagnostics, steps, skip_elems, q)
     box = _sampler_box(project, starts, held, bounds)
+    ladder = _temperature_ladder_arguments(temperature, swap_every, starts, int(steps), sampler, recalc_hess_alg, draws, box)
     sfs = list(project.scale_factors.values()) if project.scale_factors is not None else []
     if energy == 'auto':
         energy = 'free_energy' if sfs and all(sf.log_prior is not None for sf in sfs) else 'rss'
     if sampler == 'host':
         return _host_chains(project, starts, hess, int(steps), temperature, step_scale, sing_val_cutoff, seeds, skip_elems, energy,
-                            recalc_hess_alg, integrator_overrides, box, diagnostics)
+                            recalc_hess_alg, integrator_overrides, box, diagnostics, ladder)
     samp = recalc = None
     if sampler == 'device_recalc':
         recalc = dict(hess=None if hess is None else np.ascontiguousarray(hess, dtype=np.float64), cutoff=float(sing_val_cutoff),
@@ -180,13 +213,87 @@ def ensemble_log_params_batch(project, params, hess=None, steps=1000, temperatur
     else:
         if hess is None:
             hess = _gauss_newton_hessians(project, starts[:1], inverse_row_sigma(project), integrator_overrides)[0]
-        if box is not None and box['any_held']:       # one matrix per chain: the masks may differ
+        if ladder is not None:                         # one matrix per chain: that of its rung
+            V, s = _ladder_axes(hess, sing_val_cutoff, ladder, step_scale, box['held'] if box is not None and box['any_held'] else None, C)
+            samp = V * s[..., None, :]
+        elif box is not None and box['any_held']:     # one matrix per chain: the masks may differ
             samp = sampling_matrix(np.broadcast_to(np.asarray(hess, dtype=float), (C, q, q)), sing_val_cutoff, temperature,
                                    step_scale, held=box['held'])
         else:
             samp = sampling_matrix(hess, sing_val_cutoff, temperature, step_scale)
-    return _device_chains(project, starts, samp, int(steps), float(temperature), seeds, int(skip_elems), energy, draws,
-                          integrator_overrides, recalc=recalc, box=box, diagnostics=diagnostics)
+    return _device_chains(project, starts, samp, int(steps), None if ladder is not None else float(temperature), seeds,
+                          int(skip_elems), energy, draws, integrator_overrides, recalc=recalc, box=box, diagnostics=diagnostics,
+                          ladder=ladder)
+
+
+def _temperature_ladder_arguments(temperature, swap_every, starts, steps, sampler, recalc_hess_alg, draws, box):
+    """``temperature=`` / ``swap_every=`` of ``ensemble_log_params_batch`` checked and laid out for the C chains: None for a
+    scalar temperature, else the dict below.  Everything a swap step needs that depends only on the arguments is made here,
+    once: per parity the mask of the lower chains and every chain's partner temperature (its own where it has no partner)."""
+    if np.ndim(temperature) == 0:
+        if swap_every is not None:
+            raise ValueError("swap_every= exchanges replicas between the rungs of a temperature ladder: give temperature= as a "
+                             "sequence (temperature_ladder(K, t_max)), not the number %r" % (temperature,))
+        return None
+    C, q = starts.shape
+    T = np.asarray(temperature, dtype=float)
+    if T.ndim != 1 or T.size < 2:
+        raise ValueError("temperature: a number or a ladder of K >= 2 temperatures, not an array of shape %s" % (T.shape,))
+    if not np.all(np.isfinite(T) & (T > 0.0)):
+        raise ValueError("temperature: every rung of the ladder must be finite and > 0, not %s" % (T,))
+    K = T.size
+    if C % K:
+        raise ValueError("%d chains are not a whole number of ladders of %d rungs" % (C, K))
+    if recalc_hess_alg or sampler == 'device_recalc':
+        raise ValueError("a temperature ladder goes with the first algorithm only: the axes of the second one scale with sqrt(T) "
+                         "and would have to travel with a swap (recalc_hess_alg=False, sampler='host' or 'device')")
+    rung, chain_T = np.arange(C) % K, np.tile(T, C // K)
+    out = dict(T=T, K=K, chain_T=chain_T, rung=rung, ladder=np.arange(C) // K, swap_every=None, n_swaps=0)
+    if swap_every is None:
+        return out
+    if int(swap_every) != swap_every or int(swap_every) < 1:
+        raise ValueError("swap_every must be a positive whole number of steps, not %r" % (swap_every,))
+    out['swap_every'], out['n_swaps'] = int(swap_every), steps // int(swap_every)
+    if draws is not None and (len(draws) != 3 or draws[2] is None):
+        raise ValueError("draws= with swap_every= takes three arrays, (z, log_u, log_u_swap): log_u_swap of shape "
+                         "(steps // swap_every, C) = %s" % ((out['n_swaps'], C),))
+    if box is not None:       # a swap exchanges whole rows: what is fixed or bounded has to be the same on both sides
+        first = lambda a: np.repeat(a.reshape(C // K, K, q)[:, :1], K, axis=1).reshape(C, q)      # noqa: E731
+        same = (np.array_equal(box['held'], first(box['held'])) and np.array_equal(box['lower'], first(box['lower']))
+                and np.array_equal(box['upper'], first(box['upper']))
+                and np.array_equal(np.where(box['held'], starts, 0.0), np.where(box['held'], first(starts), 0.0)))
+        if not same:
+            raise ValueError("swap_every=: a swap exchanges whole parameter rows, so the held mask, the start values of the "
+                             "held columns and the bounds must be equal within every ladder")
+    lower = np.stack([(rung % 2 == parity) & (rung + 1 < K) for parity in (0, 1)])                 # (2, C)
+    partner = np.where(lower, np.arange(C) + 1, np.where(np.roll(lower, 1, axis=1), np.arange(C) - 1, np.arange(C)))
+    out.update(lower=lower, partner_T=chain_T[partner])
+    return out
+
+
+def _ladder_axes(hess, cutoff, ladder, step_scale, held_m, C):
+    """``sampling_axes`` of the C chains of temperature ladders, V (C, q, q) and s (C, q): chain c gets the axes of
+    ``hess`` (q, q) at its rung's temperature (and with its own held mask, ``held_m`` (C, q) or None)."""
+    hess = np.asarray(hess, dtype=float)
+    q, K = hess.shape[-1], ladder['K']
+    V, s = np.empty((C, q, q)), np.empty((C, q))
+    for k, T in enumerate(ladder['T']):
+        if held_m is None:
+            V[k::K], s[k::K] = sampling_axes(hess, cutoff, T, step_scale)
+        else:
+            V[k::K], s[k::K] = sampling_axes(np.broadcast_to(hess, (C // K, q, q)), cutoff, T, step_scale, held=held_m[k::K])
+    return V, s
+
+
+def _ladder_summary(ladder, n_swapped):
+    """The last element of a tempered run's return value (``ensemble_log_params_batch``); attempts depend only on the number
+    of swap steps, so they are counted here"""
+    n = ladder['n_swaps']
+    attempted = np.zeros(ladder['chain_T'].shape, dtype=np.int64)
+    if n:
+        attempted = (n + 1) // 2 * ladder['lower'][0].astype(np.int64) + n // 2 * ladder['lower'][1].astype(np.int64)
+    return dict(temperature=ladder['chain_T'].copy(), rung=ladder['rung'].copy(), ladder=ladder['ladder'].copy(),
+                swap_attempted=attempted, swap_accepted=np.asarray(n_swapped, dtype=np.int64))
 
 
 def _check_sampler_arguments(sampler, recalc_hess_alg, draws, diagnostics, steps, skip_elems, q):
@@ -218,16 +325,24 @@ def _sampler_box(project, starts, held, bounds):
 
 
 def _host_chains(project, starts, hess, steps, temperature, step_scale, sing_val_cutoff, seeds, skip_elems, energy,
-                 recalc_hess_alg, integrator_overrides, box, diagnostics):
+                 recalc_hess_alg, integrator_overrides, box, diagnostics, ladder=None):
     """The loop of ``ensemble_log_params_batch(sampler='host')``: candidates, acceptance and the record in numpy around one
-    batched device evaluation per step (two with ``recalc_hess_alg``: the Jacobians of the trial points)."""
+    batched device evaluation per step (two with ``recalc_hess_alg``: the Jacobians of the trial points).  ``ladder``
+    (``_temperature_ladder_arguments``): ``temperature`` becomes the chains' own (C,), and every ``swap_every``-th step ends
+    with a replica exchange (``_host_swap``), for 'free_energy' after one more evaluation of the current points at the
+    partners' temperatures."""
     C, q = starts.shape
     rng = np.random.default_rng(seeds)
     held_m = box['held'] if box is not None else None
+    if ladder is not None:
+        temperature = ladder['chain_T']
+        # a second stream for the swaps, a child of the first one's seed: the first delivers the numbers it always did
+        swap_rng = np.random.default_rng(rng.bit_generator.seed_seq.spawn(1)[0])
+        n_swapped, n_swaps = np.zeros(C, dtype=np.int64), 0
 
-    def F(th):
+    def F(th, T=temperature):
         if energy == 'free_energy':
-            return project.free_energy_batch(th, temperature, **integrator_overrides)
+            return project.free_energy_batch(th, T, **integrator_overrides)
         out = 0.5 * project.evaluate_batch(th, **integrator_overrides)['norms']
         return np.where(np.isfinite(out), out, np.inf)
 
@@ -238,9 +353,12 @@ def _host_chains(project, starts, hess, steps, temperature, step_scale, sing_val
         hess = hessians(starts[:1])[0]
     curr = starts.copy()
     curr_F = F(curr)
-    # one Hessian per chain, the given one broadcast: numpy's batched eigh takes the matrices one by one
-    V, sv = sampling_axes(hessians(curr) if hess is None else np.broadcast_to(np.asarray(hess, dtype=float), (C, q, q)),
-                          sing_val_cutoff, temperature, step_scale, held=held_m)
+    if ladder is not None:
+        V, sv = _ladder_axes(hess, sing_val_cutoff, ladder, step_scale, held_m, C)
+    else:
+        # one Hessian per chain, the given one broadcast: numpy's batched eigh takes the matrices one by one
+        V, sv = sampling_axes(hessians(curr) if hess is None else np.broadcast_to(np.asarray(hess, dtype=float), (C, q, q)),
+                              sing_val_cutoff, temperature, step_scale, held=held_m)
     ens, ens_F = [curr.copy()], [curr_F.copy()]
     accepted = np.zeros(C)
     for step in range(1, steps + 1):
@@ -273,14 +391,58 @@ def _host_chains(project, starts, hess, steps, temperature, step_scale, sing_val
             V = np.where(acc[:, None, None], Vn, V)
             sv = np.where(acc[:, None], sn, sv)
         accepted += acc
+        if ladder is not None and ladder['swap_every'] and step % ladder['swap_every'] == 0:
+            parity = n_swaps % 2
+            F_cross = F(curr, ladder['partner_T'][parity]) if energy == 'free_energy' else curr_F
+            curr, curr_F = _host_swap(ladder, parity, curr, curr_F, F_cross, np.log(swap_rng.random(C)), n_swapped)
+            n_swaps += 1
         if step % (skip_elems + 1) == 0:
             ens.append(curr.copy())
             ens_F.append(curr_F.copy())
     out = np.stack(ens), np.stack(ens_F), accepted / max(steps, 1)
+    if ladder is not None:      # convergence is a question to the chains of one temperature: rung 0
+        K = ladder['K']
+        diag = (ensemble_diagnostics(np.ascontiguousarray(out[0][:, ::K]), np.ascontiguousarray(out[1][:, ::K])),) if diagnostics else ()
+        return out + diag + (_ladder_summary(ladder, n_swapped),)
     return out + (ensemble_diagnostics(out[0], out[1]),) if diagnostics else out
 
 
+def _host_swap(ladder, parity, curr, curr_F, F_cross, log_u, n_swapped):
+    """One replica-exchange step in numpy (``ensemble_log_params_batch``, ``swap_every``): new (curr, curr_F); ``n_swapped``
+    is counted in place at the lower chains.  The rule and its order of evaluation are those of ``sbm_pt_swap``."""
+    i = np.flatnonzero(ladder['lower'][parity])
+    j, T = i + 1, ladder['chain_T']
+    with np.errstate(over='ignore', invalid='ignore'):
+        bound = (curr_F[i] - F_cross[j]) / T[i] + (curr_F[j] - F_cross[i]) / T[j]
+        take = np.isfinite(F_cross[i]) & np.isfinite(F_cross[j]) & (log_u[i] < bound)
+    i, j = i[take], j[take]
+    curr, new_F = curr.copy(), curr_F.copy()
+    curr[i], curr[j] = curr[j].copy(), curr[i].copy()
+    new_F[i], new_F[j] = F_cross[j], F_cross[i]
+    n_swapped[i] += 1
+    return curr, new_F
+
+
 _DRAW_BLOCK = 256      # steps whose random numbers are drawn at once
+
+
+def _swap_draws(draws, seeds, n_swaps, C, dev):
+    """The log-uniform numbers of the device loop's swap steps, (n_swaps, C) on the device: ``draws[2]`` when given, else from
+    a second ``torch.Generator``, seeded with a child of ``seeds`` -- the generator of ``_step_draws`` is not touched."""
+    import torch
+    if draws is not None:
+        u = torch.as_tensor(draws[2] if isinstance(draws[2], torch.Tensor) else np.asarray(draws[2], dtype=np.float64))
+        u = u.to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(u.shape) != (n_swaps, C):
+            raise ValueError("draws: log_u_swap must have shape (steps // swap_every, C) = %s, not %s" % ((n_swaps, C), tuple(u.shape)))
+        return u
+    gen = torch.Generator(device=dev)
+    if seeds is None:
+        gen.seed()
+    else:
+        child = np.random.SeedSequence(seeds).spawn(1)[0]
+        gen.manual_seed(int(child.generate_state(1, dtype=np.uint64)[0] >> np.uint64(1)))
+    return torch.log(torch.rand((n_swaps, C), dtype=torch.float64, device=dev, generator=gen))
 
 
 def _step_draws(draws, seeds, steps, C, q, dev):
@@ -310,7 +472,7 @@ def _step_draws(draws, seeds, steps, C, q, dev):
 
 
 def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems, energy, draws, overrides, recalc=None,
-                   box=None, diagnostics=False):
+                   box=None, diagnostics=False, ladder=None):
     """The loop of ``ensemble_log_params_batch(sampler='device')``: per step ``mh_propose``, the evaluation and ``mh_accept``
     (project/_evaluation.py) enqueued on the context's stream and no read-back; the record is a preallocated device array
     that the acceptance writes every (skip_elems + 1)-th step.
@@ -320,7 +482,10 @@ def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems,
     ``box`` = dict(held, lower, upper, ...) (``held=`` / ``bounds=``): the proposal is ``sbm_mh_propose_box`` (``samp`` (C, q, q)
     goes per chain), its ``outside`` flags veto the chains in the acceptance, the axes are those of the free columns.  What
     is absent is None and reaches the library as NULL: without a box, the kernels and the bits of the loop before it had one.
-    ``diagnostics``: two more enqueues per record (``_ensemble_diagnostics_dev``) ahead of the one synchronisation."""
+    ``diagnostics``: two more enqueues per record (``_ensemble_diagnostics_dev``) ahead of the one synchronisation.
+    ``ladder`` (``_temperature_ladder_arguments``; ``temperature`` is then None): the chains' temperatures are a device array
+    and the entropy and the acceptance the ``_pt`` entries; a swap step is ``pt_swap`` after, for 'free_energy', one more
+    state-only evaluation of ``curr`` and the entropy at the partners' temperatures -- enqueued like the rest."""
     import torch
     ev = DeviceEvaluator(project)
     dev = ev.dev
@@ -356,9 +521,19 @@ def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems,
     lower_d, upper_d = (to_dev(box['lower']), to_dev(box['upper'])) if box is not None and box['bounded'] else (None, None)
     outside = torch.empty((C,), dtype=i32, device=dev) if box is not None else None
     opts = None if host_loop else project._opts(**overrides)
+    swaps = partner_T = entropy_x = n_swapped = None
+    if ladder is not None:
+        temperature = to_dev(ladder['chain_T'])
+        if ladder['n_swaps']:
+            swaps = _swap_draws(draws, seeds, ladder['n_swaps'], C, dev)
+            n_swapped = torch.zeros((C,), dtype=i32, device=dev)
+            if free:
+                partner_T = [to_dev(t) for t in ladder['partner_T']]
+                entropy_x = torch.empty((C,), dtype=f64, device=dev)
 
-    def evaluate(th):
-        """norms, status (and sims) of the C points ``th``; entropy of their simulations; with ``recalc`` their Jacobians"""
+    def evaluate(th, T=temperature, entropy=entropy):
+        """norms, status (and sims) of the C points ``th``; entropy of their simulations at ``T``, a number or one per chain;
+        with ``recalc`` their Jacobians"""
         if host_loop:
             if recalc is not None:
                 res = project.evaluate_batch(th, jacobian=True, want=('sims', 'norms', 'status', 'jacobian'), **overrides)
@@ -369,8 +544,11 @@ def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems,
         else:
             ev.run(th, opts, buf, recalc is not None)
             nr, st, sm = buf['norms'], buf['status'], buf['sims']
-        if free:
-            _lib.check(ev.lib.sbm_project_sf_entropy(ev.proj, _lib.dev_ptr(sm), C, temperature, _lib.dev_ptr(entropy), None),
+        if free and ladder is not None:
+            _lib.check(ev.lib.sbm_project_sf_entropy_pt(ev.proj, _lib.dev_ptr(sm), C, _lib.dev_ptr(T), _lib.dev_ptr(entropy), None),
+                       'sbm_project_sf_entropy_pt')
+        elif free:
+            _lib.check(ev.lib.sbm_project_sf_entropy(ev.proj, _lib.dev_ptr(sm), C, T, _lib.dev_ptr(entropy), None),
                        'sbm_project_sf_entropy')
         return nr, st
 
@@ -399,11 +577,28 @@ def _device_chains(project, starts, samp, steps, temperature, seeds, skip_elems,
                   F_curr=F_curr, n_accepted=n_acc, ens_slot=ens[step // every] if kept else None,
                   ens_F_slot=ens_F[step // every] if kept else None, veto=outside, axes_curr=ax_c, axes_trial=ax_t,
                   axes_status=ax_status)
-    diag = _ensemble_diagnostics_dev(ctx, ens, ens_F, None, 1) if diagnostics else None
+        if swaps is not None and step % ladder['swap_every'] == 0:
+            n = step // ladder['swap_every'] - 1                   # the n-th swap step, from 0
+            F_cross = None
+            if free:
+                nr, st = evaluate(curr, partner_T[n % 2], entropy_x)
+                F_cross = finite_cost(nr, st, entropy_x).contiguous()
+            pt_swap(ctx, K=ladder['K'], parity=n % 2, temperature=temperature, F_cross=F_cross, log_u=swaps[n], curr=curr,
+                    F_curr=F_curr, n_swapped=n_swapped, ens_slot=ens[step // every] if kept else None,
+                    ens_F_slot=ens_F[step // every] if kept else None)
+    if ladder is not None and diagnostics:      # the chains of rung 0: one temperature
+        K = ladder['K']
+        diag = _ensemble_diagnostics_dev(ctx, ens[:, ::K].contiguous(), ens_F[:, ::K].contiguous(), None, 1)
+    else:
+        diag = _ensemble_diagnostics_dev(ctx, ens, ens_F, None, 1) if diagnostics else None
     ctx.synchronize()
     torch.cuda.synchronize(dev)
     out = ens.cpu().numpy(), ens_F.cpu().numpy(), n_acc.cpu().numpy() / max(steps, 1)
-    return out + ({k: v.cpu().numpy() for k, v in diag.items()},) if diagnostics else out
+    if diagnostics:
+        out += ({k: v.cpu().numpy() for k, v in diag.items()},)
+    if ladder is not None:
+        out += (_ladder_summary(ladder, n_swapped.cpu().numpy() if n_swapped is not None else np.zeros(C, dtype=np.int64)),)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------
